@@ -14,7 +14,8 @@ registrations/s over all ranks (weak scaling: every rank registers its own scan 
 own copy of the submap; the only exchange is one all-gather of the K result records per rank at the
 end — SURVEY.md §8e).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR also writes what the
+last timed step returned (dump_outputs).  With --full the JSON line also carries
   roofline       derivative kernel: algorithmic bytes per launch / hipEvent-measured launch
                  duration vs 8 TB/s, next to the HBM bytes the PMC counters saw (profiles/pmc_ndt_eval_latest.json);
   cpu_baseline   the CPU oracle (C++/OpenMP restatement of ndt_omp — NOT ndt_omp itself) on this box's host cores;
@@ -54,10 +55,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--stream", type=int, default=50, help="scans in the latency-statistics stream (>= 50)")
-    ap.add_argument("--candidates", type=int, default=64, help="loop-closure candidates of the cfg 4 leg")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (roofline, cfg 3/4/5, streams, loop gate, CPU baseline); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--stream", type=int, default=50, help="--full: scans in the latency-statistics stream (>= 50)")
+    ap.add_argument("--candidates", type=int, default=64, help="--full: loop-closure candidates of the cfg 4 leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: headline + roofline only")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--workers", type=int, default=0, help="workload-generation processes (default: host threads / ranks, <= 64)")
     return ap.parse_args()
@@ -182,6 +187,17 @@ def lat_stats(ts):
             "registrations_per_s": float(1e3 / np.median(ts))}
 
 
+def dump_outputs(d, final, res):
+    """--dump-outputs: what lsr_align hands its caller for the last timed step — the final transformation (row-major 4x4) and
+    the lsr_result fields (gpu_ms, a timing, left out) — one DIR/<name>.npy each, so that two builds can be compared."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"final_transformation": np.asarray(final, np.float32), "score": np.float64(res.score),
+              "iterations": np.float64(res.iterations), "converged": np.float64(res.converged),
+              "n_evaluations": np.float64(res.n_evaluations), "n_correspondences": np.float64(res.n_correspondences)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a))
+
+
 def _candidate_job(c):
     from lidarslam_ros2_amd import synth
 
@@ -197,7 +213,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    extras = (not args.no_extras)
+    extras = args.full and not args.no_extras
 
     # ---- workloads first: generated by forked worker processes BEFORE this process touches the GPU
     from lidarslam_ros2_amd import synth
@@ -369,6 +385,8 @@ def main():
     last = ndt.last_result
     j_last = (args.warmup + args.steps - 1) % nss
     gpu_final = fin16.reshape(4, 4).T.copy()   # final transformation of the last timed registration
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gpu_final, ndt._last)
     err_t, err_r = pose_delta(gpu_final, stream[j_last][2])
     value = world * args.steps / elapsed
 
@@ -397,7 +415,7 @@ def main():
     # ------------------------------------------------------------------------------------------------------------
     # ---- roofline of the dominant kernel (K3+K4 derivative pass), hipEvents around the launch chains (rank 0; before the
     # multi-rank leg so that it is in the line whatever happens there)
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             out["roofline"] = roofline_leg(ndt, step, n_src_pts, grid)
         except Exception as e:
@@ -499,7 +517,7 @@ def main():
                     out[name] = fn()
                 except Exception as e:
                     out[name] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             try:
                 cpu_leg(args, out, stash, case, stream, j_last, gpu_final, res, max_iter)
             except Exception as e:

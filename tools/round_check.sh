@@ -1,5 +1,5 @@
 #!/bin/bash
-# What the driver runs at round end, in one GPU session, plus the cfg-4 stage timings: the whole GPU suite, the C-entry stage probe (64 and 8 candidates), one default bench line.
+# At round end, in one GPU session: the whole GPU suite, the C-entry stage probe (64 and 8 candidates), one full bench line (--full).
 set -u
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 O=$REPO/gpurun_out/round_check
@@ -9,7 +9,7 @@ export LSR_BENCH_CACHE_DIR=/tmp/lsr_bench_cache
 (timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -25) > $O/pytest.log; tail -8 $O/pytest.log | cut -c1-400
 (timeout 600 python tools/cfg4_stage_probe.py 2>&1 | tail -2) | tee $O/stage64.log
 (NC=8 timeout 600 python tools/cfg4_stage_probe.py 2>&1 | tail -2) | tee $O/stage8.log
-(timeout 900 python bench.py > $O/bench.json 2> $O/bench.err); echo "bench rc=$?"; tail -3 $O/bench.err
+(timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err); echo "bench rc=$?"; tail -3 $O/bench.err
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ.get("GRAFT_REPO_ROOT","/root/repo")+"/gpurun_out/round_check/bench.json").read().strip().splitlines()[-1])

@@ -26,8 +26,8 @@ bash tools/pmc_cfg5.sh > $P/pmc_cfg5.log 2>&1
 for f in gpurun_out/pmc_cfg5/csv/*.csv; do cp $f $P/${TAG}_pmc_csv/cfg5_$(basename $f); done
 bash tools/pmc_builders.sh $TAG > $P/pmc_builders.log 2>&1
 cp gpurun_out/pmc_builders/${TAG}_pmc_builders.md $P/; cp gpurun_out/pmc_builders/csv/*.csv $P/${TAG}_pmc_csv/ 2>/dev/null
-# 2. default bench run (the driver's command), JSON line kept
-timeout 900 python bench.py > $P/${TAG}_bench_final.json 2> $P/bench.err; echo "bench rc=$?"
+# 2. full bench run (every leg), JSON line kept
+timeout 900 python bench.py --full > $P/${TAG}_bench_final.json 2> $P/bench.err; echo "bench rc=$?"
 # 3. kernel-trace summaries
 stats() {  # name, command...
   name=$1; shift
@@ -35,7 +35,7 @@ stats() {  # name, command...
   cp /tmp/prof_$name/${name}_kernel_stats.csv $P/${TAG}_rocprofv3_${name}_kernel_stats.csv   # the raw summary, as rocprofv3 wrote it
   { echo "# rocprofv3 --kernel-trace --stats -- $* ($TAG, MI355X; raw CSV: ${TAG}_rocprofv3_${name}_kernel_stats.csv)"; echo; python tools/stats_to_md.py /tmp/prof_$name/${name}_kernel_stats.csv 30; echo; echo '```'; grep -v "^W2\|^E2\|amdgpu.ids" $P/$name.stdout | tail -8 | cut -c1-2500; echo '```'; } > $P/${TAG}_rocprofv3_${name}_stats.md
 }
-stats bench python $REPO/bench.py
+stats bench python $REPO/bench.py --full
 stats gicp python $REPO/tools/gicp_probe.py
 stats cfg4 python $REPO/tools/cfg4_probe.py
 stats target python $REPO/tools/target_probe.py
@@ -59,7 +59,7 @@ if [ "${LSR_PROFILE_MICRO:-0}" = "1" ]; then   # micro-benchmarks behind profile
 (LSR_LIB_NAME=liblidarslam_reg_timing.so timeout 400 python tools/timing_probe.py 2>&1 | grep -v amdgpu.ids) > $P/${TAG}_timing_probe.txt
 fi
 # 4. two ranks sharing this one device (gloo): exercises the self-spawn + sharded C-ABI path
-LSR_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 2 --steps 20 --warmup 3 > $P/${TAG}_bench_2ranks_one_device.json 2> $P/bench2.err; echo "bench2 rc=$?"
+LSR_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 2 --steps 20 --warmup 3 > $P/${TAG}_bench_2ranks_one_device.json 2> $P/bench2.err; echo "bench2 rc=$?"
 rm -f $P/*.stderr
 # the raw rocprofv3 trees are tens of MB each (gpurun merges at most 64 MiB back): what is kept of them is under $P
 rm -rf gpurun_out/pmc_ndt gpurun_out/pmc_gicp gpurun_out/pmc_cfg5 gpurun_out/pmc_builders
