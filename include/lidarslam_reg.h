@@ -50,7 +50,10 @@ typedef enum lsr_method { LSR_METHOD_NDT = 0, LSR_METHOD_GICP = 1 } lsr_method;
 /* pclomp::NeighborSearchMethod, selected at scanmatcher_component.cpp:110 (the reference only ever selects DIRECT7).
  * KDTREE (round 6): ndt_omp's radiusSearch(x', resolution) over the kd-tree of the leaves' float centroids, restated as the 27 cells
  * around the point's cell filtered by the kd-tree's own test (FLANN L2_Simple<float> strictly below (float)(resolution^2)) — a
- * centroid lies inside its own cell, so no leaf outside those cells can pass.  The centroids are built on first use. */
+ * centroid lies inside its own cell, so no leaf outside those cells can pass.  The kd-tree holds every leaf with >= 6 points, those
+ * the eigen check invalidated (npts = -1) included: pclomp pushes the centroid before that check and neither radiusSearch() nor
+ * computeDerivatives() tests nr_points, so such a leaf is a neighbour with its constructor icov of 0 — it adds -d1 to the score and
+ * nothing to the gradient or Hessian (the DIRECT lookups skip it).  The centroids are built on first use. */
 typedef enum lsr_neighborhood { LSR_KDTREE = 0, LSR_DIRECT26 = 1, LSR_DIRECT7 = 2, LSR_DIRECT1 = 3 } lsr_neighborhood;
 
 typedef enum lsr_key {
@@ -384,7 +387,8 @@ int lsr_ndt_grid_info(lsr_handle h, int32_t* info8);
 int lsr_ndt_grid_dump(lsr_handle h, int32_t* idx, int32_t* npts, double* mean, double* icov);
 /* The FLOAT centroids of the leaves (pclomp::VoxelGridCovariance::Leaf::centroid: the float running sum of a leaf's points in cloud
  * order over (float) count) — the points of the voxel-centroid kd-tree that the KDTREE neighbourhood searches —, in the order of
- * lsr_ndt_grid_dump: centroid[L*3]; NaN for leaves that are not in the kd-tree (fewer than 6 points, invalid covariance). */
+ * lsr_ndt_grid_dump: centroid[L*3]; NaN for leaves that are not in the kd-tree (fewer than 6 points).  Leaves whose covariance the
+ * eigen check invalidated (npts = -1) are in the kd-tree and have their centroid. */
 int lsr_ndt_grid_centroids(lsr_handle h, float* centroid);
 /* One derivative pass at pose p = (tx,ty,tz,rx,ry,rz); T16 (nullable, col-major) overrides the point
  * transform like the first pass of align().  grad: 6, hess: 36 (row-major). */

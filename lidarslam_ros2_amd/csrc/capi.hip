@@ -1937,7 +1937,7 @@ int lsr_ndt_grid_centroids(lsr_handle h, float* centroid) {
   int c = 0;
   for (int r = 0; r < L; r++) {
     if (keys[r] < 0) continue;
-    const int s = slot[(size_t)keys[r]];
+    const int s = kd_slot(slot[(size_t)keys[r]]);
     for (int k = 0; k < 3; k++) centroid[c * 3 + k] = (s >= 0) ? cen[(size_t)s * 4 + k] : std::numeric_limits<float>::quiet_NaN();
     c++;
   }

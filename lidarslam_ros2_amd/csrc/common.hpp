@@ -136,7 +136,7 @@ struct VoxelGridDev {
   int n_leaves = 0;        // occupied leaves (any count)
   int n_valid = 0;         // leaves usable by lookups
   bool dense = false;      // rec[] indexed by cell (dense) or by leaf slot (compact)
-  DevBuf<int> cell_slot;   // dense [ncells] -> record slot or -1
+  DevBuf<int> cell_slot;   // dense [ncells] -> record slot, -1, or -2 - slot for an invalidated leaf (ndt.hpp: cell_slot_code)
   DevBuf<float4> rec;      // [n_leaves * 4]
   // LDS image of the valid-voxel table (ndt_pack_lds_table): uint16 cell->slot map (0xFFFF = none) followed by 48-byte
   // records of the usable leaves; lds_bytes == 0 when the table is too large to stage
@@ -145,9 +145,9 @@ struct VoxelGridDev {
   // fp64 copies for inspection/parity (mean 3, icov 9 row-major) + key + count per leaf
   DevBuf<double> mean64, icov64;
   DevBuf<int> leaf_key, leaf_n;
-  // KDTREE neighbourhood only (built on first use, ndt_build_centroids): Leaf::centroid of every usable leaf — the FLOAT running sum
-  // of its points in cloud order over (float) count, what the reference's voxel-centroid kd-tree holds — indexed like rec[] (by
-  // cell_slot[cell]); .w unused
+  // KDTREE neighbourhood only (built on first use, ndt_build_centroids): Leaf::centroid of every leaf in the kd-tree (>= min_points
+  // points, invalidated ones included) — the FLOAT running sum of its points in cloud order over (float) count, what the reference's
+  // voxel-centroid kd-tree holds — indexed like rec[] (by kd_slot(cell_slot[cell])); .w unused
   DevBuf<float4> centroid;
   // what the counting-sort builder leaves behind (dense key spaces): the target's points in cell order (x | y | z planes of
   // `sorted_pitch` floats), their original indices, the start of every cell (ncells + 2 entries: [ncells] = first non-finite

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void leaf_finalize_kernel(const double* __rest
       for (int k = 0; k < 9; k++) icov64[(size_t)r * 9 + k] = icov[k];
       const size_t ri = dense ? (size_t)key : (size_t)r;  // dense: record lives at its cell index
       leaf_record_dev(mean, icov, n, valid, rec + ri * 4);
-      cell_slot[key] = valid ? (int)ri : -1;
+      cell_slot[key] = cell_slot_code(valid, n, (int)ri);
     }
   }
   // one atomic per wave: device-scope atomics on one address are served one after the other, ~13 ns each (15 000 leaves: 0.2 ms)
@@ -503,8 +503,8 @@ __global__ __launch_bounds__(256) void leaf_centroid_seq_kernel(const float* __r
   if (r >= *n_runs_dev) return;
   const unsigned int key = run_key[r];
   if (key == sentinel) return;          // the run of the non-finite points
-  const int slot = cell_slot[key];
-  if (slot < 0) return;                 // fewer than min_points_per_voxel points / invalid covariance: not in the kd-tree
+  const int slot = kd_slot(cell_slot[key]);
+  if (slot < 0) return;                 // fewer than min_points_per_voxel points: not in the kd-tree (an invalidated leaf is)
   const int beg = run_off[r], end = run_off[r + 1];
   float sx = 0.f, sy = 0.f, sz = 0.f;
   for (int j = beg; j < end; j++) {

@@ -336,7 +336,7 @@ __device__ __forceinline__ void vg_leaf_kernel_body(const float* __restrict__ sx
   for (int k = 0; k < 3; k++) mean64[(size_t)cell * 3 + k] = mean[k];
   for (int k = 0; k < 9; k++) icov64[(size_t)cell * 9 + k] = icov[k];
   leaf_record_dev(mean, icov, n, valid, rec + (size_t)cell * 4);
-  cell_slot[cell] = valid ? cell : -1;
+  cell_slot[cell] = cell_slot_code(valid, n, cell);
 }
 __global__ __launch_bounds__(VG_LEAF_THREADS) void vg_leaf_kernel(const float* __restrict__ sx, const float* __restrict__ sy,
                                                                   const float* __restrict__ sz, const unsigned int* __restrict__ start,
@@ -369,7 +369,7 @@ __device__ __forceinline__ void vg_leaf_finish_body(const unsigned int* __restri
   for (int k = 0; k < 3; k++) mean64[(size_t)cell * 3 + k] = mean[k];
   for (int k = 0; k < 9; k++) icov64[(size_t)cell * 9 + k] = icov[k];
   leaf_record_dev(mean, icov, n, valid, rec + (size_t)cell * 4);
-  cell_slot[cell] = valid ? cell : -1;
+  cell_slot[cell] = cell_slot_code(valid, n, cell);
 }
 
 // ---- the same builders over a GROUP of targets: blockIdx.y selects the member, whose parameters travel in the kernel arguments ----

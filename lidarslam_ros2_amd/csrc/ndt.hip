@@ -1134,10 +1134,11 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
         if (tid >= THREADS - 6) s_box[THREADS - 1 - tid] = (THREADS - 1 - tid < 3) ? INT_MAX : INT_MIN;
       }
 
-      bool valid[NT];
+      bool valid[NT], score_only[NT];
       int cellv[NT];
 #pragma unroll
       for (int t = 0; t < NT; t++) {
+        score_only[t] = false;
         const int o = ql + 4 * t;  // this lane's t-th neighbour
         int dx, dy, dz;
         Offsets<NOFF>::get(o, dx, dy, dz);
@@ -1152,9 +1153,10 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
                   // the kd-tree's radius search would return
 #pragma unroll
         for (int t = 0; t < NT; t++) {
-          const int sl = valid[t] ? P.cell_slot[cellv[t]] : -1;
+          const int code = valid[t] ? P.cell_slot[cellv[t]] : -1, sl = kd_slot(code);
           const float4 cen = P.centroid[sl >= 0 ? sl : 0];
           valid[t] = (sl >= 0) & centroid_in_radius(tx, ty, tz, cen.x, cen.y, cen.z, P.radius2);
+          score_only[t] = valid[t] & (code < -1);   // an invalidated leaf in the kd-tree (the table below has no record for it)
         }
       }
       float4 r0[NT], r1[NT], r2[NT];
@@ -1199,6 +1201,16 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
         }
       }
 
+      if (KD) {   // a score-only neighbour: pclomp's Leaf of nr_points = -1 keeps icov_ = 0 — the pair adds exp(0) = 1 times -d1
+                  // to the score (d2 * 1 passes the range test) and nothing to the A / E sums; its mean drops out of q' C q
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          if (score_only[t]) {
+            valid[t] = true;
+            r0[t] = r1[t] = r2[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+        }
+      }
       float score = 0.f, npairs = 0.f;
       float A0 = 0.f, A1 = 0.f, A2 = 0.f;
       float E00 = 0.f, E01 = 0.f, E02 = 0.f, E11 = 0.f, E12 = 0.f, E22 = 0.f;
@@ -1508,7 +1520,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
 
     // every neighbour's record address first: NOFF cell -> slot lookups in flight at once (one LDS round trip), so that the
     // record gathers below depend on nothing but their own address
-    bool nb_ok[NOFF];
+    bool nb_ok[NOFF], nb_so[NOFF];   // nb_so: a score-only neighbour (KDTREE: an invalidated leaf in the kd-tree)
     int nb_rec[NOFF];     // LDS table: byte offset of the record inside the table image; global tables: record index
 #pragma unroll
     for (int o = 0; o < NOFF; o++) {
@@ -1517,14 +1529,16 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
       const bool in = inx[dx + 1] & iny[dy + 1] & inz[dz + 1];
       const int cell = in ? centre + dx + dy * mul1 + dz * mul2 : 0;
       nb_ok[o] = in;
+      nb_so[o] = false;
       nb_rec[o] = cell;
     }
     if (KD) {   // KDTREE (a template form of its own): of the 27 cells, the leaves whose centroid the kd-tree's radius search would return
 #pragma unroll
       for (int o = 0; o < NOFF; o++) {
-        const int ks = nb_ok[o] ? P.cell_slot[nb_rec[o]] : -1;
+        const int code = nb_ok[o] ? P.cell_slot[nb_rec[o]] : -1, ks = kd_slot(code);
         const float4 cen = P.centroid[ks >= 0 ? ks : 0];
         nb_ok[o] = (ks >= 0) & centroid_in_radius(tx, ty, tz, cen.x, cen.y, cen.z, P.radius2);
+        nb_so[o] = nb_ok[o] & (code < -1);
       }
     }
     if (TAB == NDT_TAB_LDS) {
@@ -1545,6 +1559,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         nb_ok[o] = nb_ok[o] & (sl[o] >= 0);
         nb_rec[o] = sl[o] >= 0 ? sl[o] : 0;
       }
+    }
+
+    if (KD) {   // score-only neighbours take the pair path with a zero record (set at the gathers below): the tables hold none for them
+#pragma unroll
+      for (int o = 0; o < NOFF; o++) nb_ok[o] = nb_ok[o] | nb_so[o];
     }
 
     // a neighbour NO lane of the wave can use (the layer above the scan, the one below the ground: a wave's 64 points are
@@ -1577,6 +1596,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
             } else {
               const GlbV4* rp = g_rec + (size_t)nb_rec[o] * 4;   // empty / unusable cells hold NaN records
               r0[u] = rp[0]; r1[u] = rp[1]; r2[u] = rp[2];
+            }
+            if (KD && nb_so[o]) {   // icov 0 (pclomp's Leaf constructor): -d1 to the score, nothing else; the mean drops out
+              const v4f z = {0.f, 0.f, 0.f, 0.f};
+              r0[u] = z; r1[u] = z; r2[u] = z;
             }
           }
         }

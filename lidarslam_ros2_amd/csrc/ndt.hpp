@@ -51,6 +51,13 @@ enum NdtTableMode : int {
 };
 constexpr int NDT_TILE_BYTES = 32 * 1024;  // tile buffer per workgroup: 682 cells of 48 bytes
 
+// cell_slot[cell]: >= 0 the record slot of a leaf lookups can use; -1 no such leaf (empty, fewer than min_points_per_voxel points);
+// -2 - slot a leaf the eigen check invalidated (nr_points = -1).  Every DIRECT lookup tests >= 0.  pclomp's kd-tree holds the latter
+// too (applyFilter pushes the centroid before the eigen check, radiusSearch() never tests nr_points): the KDTREE search finds them by
+// kd_slot() and takes them as score-only neighbours (icov 0).
+__host__ __device__ inline int cell_slot_code(bool usable, int n, int slot) { return usable ? slot : (n < 0 ? -2 - slot : -1); }
+__host__ __device__ inline int kd_slot(int code) { return code >= -1 ? code : -2 - code; }
+
 struct NdtState {
   // ---- evaluation request, read by every workgroup of the next launch
   float T[12];       // row-major 3x4 point transform

@@ -32,6 +32,7 @@ namespace {
 
 struct Leaf {
   int n = 0;            // nr_points (-1 = invalidated)
+  bool in_tree = false; // >= min_points_per_voxel points: the centroid is in the kd-tree of the KDTREE search, invalidated or not
   double sum[3] = {0, 0, 0};     // running sum of points (mean_ before normalisation)
   float csum[3] = {0.f, 0.f, 0.f};   // Leaf::centroid: the FLOAT running sum of the points, in cloud order ("leaf.centroid += pt")
   float centroid[3] = {0.f, 0.f, 0.f};   // ... normalised by (float)nr_points: the point the voxel-centroid kd-tree holds (KDTREE search)
@@ -111,6 +112,10 @@ Grid* grid_build(const float* pts, size_t stride_f, size_t n, float leaf) {
     for (int a = 0; a < 3; a++) L.mean[a] = L.sum[a] / nn;
     for (int a = 0; a < 3; a++) L.centroid[a] = L.csum[a] / (float)L.n;   // "leaf.centroid /= static_cast<float>(leaf.nr_points)"
     if (L.n < g->min_points) continue;
+    // applyFilter pushes the centroid into the kd-tree cloud here, BEFORE the eigen check below may set nr_points = -1: an
+    // invalidated leaf stays in the tree with Leaf's constructor icov_ = 0
+    L.in_tree = true;
+    for (int a = 0; a < 9; a++) L.icov[a] = 0.0;
     for (int a = 0; a < 3; a++)
       for (int b = 0; b < 3; b++)
         L.cov[a * 3 + b] = (L.sq[a * 3 + b] - 2.0 * (L.sum[a] * L.mean[b])) / nn + L.mean[a] * L.mean[b];
@@ -142,8 +147,10 @@ Grid* grid_build(const float* pts, size_t stride_f, size_t n, float leaf) {
       mnc = std::min(mnc, L.icov[a]);
       if (L.icov[a] != L.icov[a]) bad = true;
     }
-    if (mxc == std::numeric_limits<double>::infinity() || mnc == -std::numeric_limits<double>::infinity() || bad)
-      L.n = -1;
+    if (mxc == std::numeric_limits<double>::infinity() || mnc == -std::numeric_limits<double>::infinity() || bad) {
+      L.n = -1;   // (pclomp keeps the non-finite inverse here; zero, as for the eigen check — DESIGN.md §4 "KDTREE"; no test reaches it)
+      for (int a = 0; a < 9; a++) L.icov[a] = 0.0;
+    }
   }
   return g;
 }
@@ -151,7 +158,8 @@ Grid* grid_build(const float* pts, size_t stride_f, size_t n, float leaf) {
 // Neighbourhood offsets.  search: 7 = DIRECT7, 1 = DIRECT1, 26 = DIRECT26
 // (DIRECT26 in ndt_omp visits the full 3x3x3 block = 27 offsets including the centre), 0 = KDTREE.
 // KDTREE (ndt_omp: target_cells_.radiusSearch(x_trans_pt, resolution_, ...) = a radius search of the kd-tree over the centroids of the
-// leaves with >= min_points_per_voxel points): every leaf whose centroid lies within `resolution` of the point.  A centroid lies inside
+// leaves with >= min_points_per_voxel points, those the eigen check invalidated included): every such leaf whose centroid lies within
+// `resolution` of the point.  A centroid lies inside
 // its own cell, so such a leaf is one of the 3 x 3 x 3 cells around the point's cell: the search is restated as those 27 cells
 // filtered by the kd-tree's own test — FLANN L2_Simple<float> (dx*dx, + dy*dy, + dz*dz in float) strictly below (float)(r*r), as
 // RadiusResultSet::addPoint compares.  (The kd-tree returns its hits sorted by distance; the order only decides in which order a
@@ -191,7 +199,10 @@ inline int neighbours(const Grid& g, const float* xt, const int off[27][3], int 
     int idx = (ijk[0] + off[o][0] - g.min_b[0]) * g.mul[0] + (ijk[1] + off[o][1] - g.min_b[1]) * g.mul[1] +
               (ijk[2] + off[o][2] - g.min_b[2]) * g.mul[2];
     auto it = g.leaves.find(idx);
-    if (it == g.leaves.end() || it->second.n < g.min_points) continue;
+    if (it == g.leaves.end()) continue;
+    // DIRECT: the getters test nr_points >= min_points.  KDTREE: radiusSearch() tests nothing — an invalidated leaf in the tree is a
+    // neighbour with icov 0 (exp(0) = 1: the pair adds -d1 to the score and nothing to the gradient or Hessian)
+    if (radius2 >= 0.f ? !it->second.in_tree : it->second.n < g.min_points) continue;
     if (radius2 >= 0.f) {   // KDTREE: the kd-tree's radius test on the leaf's float centroid
       const Leaf& L = it->second;
       float d = 0.f;

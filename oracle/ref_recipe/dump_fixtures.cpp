@@ -73,6 +73,15 @@ struct NdtProbe : pclomp::NormalDistributionsTransform<Point, Point> {
     return this->computeDerivatives(grad, hess, moved, p, true);
   }
   const Base::TargetGrid& cells() const { return this->target_cells_; }
+  // the kd-tree's own point cloud (VoxelGridCovariance::getCentroids(), leaf-map order): which leaves the KDTREE search can return is
+  // read from here, never inferred from nr_points
+  std::vector<double> kd_cloud() {
+    std::vector<double> v;
+    const auto c = this->target_cells_.getCentroids();
+    if (c)
+      for (std::size_t i = 0; i < c->size(); i++) { v.push_back((*c)[i].x); v.push_back((*c)[i].y); v.push_back((*c)[i].z); }
+    return v;
+  }
 };
 struct GicpProbe : pclomp::GeneralizedIterativeClosestPoint<Point, Point> {
   int iterations() const { return this->nr_iterations_; }   // pcl::Registration keeps the count protected
@@ -148,11 +157,60 @@ int main(int argc, char** argv) {
     put(f, "grad_kdtree", g.data(), 6);
     for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) Hrow[r * 6 + c] = H(r, c);
     put(f, "hess_kdtree", Hrow, 36);
-    std::vector<double> cen;   // Leaf::centroid (Eigen::VectorXf) of every leaf, ascending leaf index; the leaves below min_points_per_voxel are not in the kd-tree
-    for (const auto& kv : ndt.cells().getLeaves())
-      for (int k = 0; k < 3; k++) cen.push_back(kv.second.nr_points >= 6 ? (double)kv.second.centroid[k] : 1e300);   // (1e300: not in the tree; JSON has no NaN)
-    put(f, "leaf_centroid", cen.data(), cen.size());
+    // the kd-tree's cloud itself; import_results.py places each point in its leaf (a centroid lies in its own cell) -> leaf_centroid
+    const std::vector<double> kd = ndt.kd_cloud();
+    put(f, "kd_cloud", kd.data(), kd.size());
+    std::fprintf(f, "\"resolution\": %.17g,\n", res);
     std::fprintf(f, "\"kdtree\": 1\n},\n");
+  }
+  {  // ---- ndt_degenerate (tests/degenerate_scene.py): plane / line leaves (clamped eigenvalues), single-point leaves (covariance 0:
+     // nr_points = -1), 5- and 6-point leaves, non-finite points.  Leaf counts incl. -1, the kd-tree's cloud, D7 and KDTREE derivatives
+     // at every pose of "poses" and a registration from the identity with each
+    const size_t at = J.find_key("ndt_degenerate", 0);
+    Cloud::Ptr tgt = load(in, J.str("target", at)), src = load(in, J.str("source", at));
+    const double res = J.number("resolution", at);
+    const std::vector<double> poses = J.array("poses", at);   // 6 per pose
+    NdtProbe ndt;
+    configure(ndt, res, 0.01, 35);
+    ndt.setInputTarget(tgt);
+    ndt.setInputSource(src);
+    Cloud aligned;
+    ndt.align(aligned, Eigen::Matrix4f::Identity());   // builds the grid and the Gauss constants
+    std::fprintf(f, "\"ndt_degenerate\": {\n");
+    std::fprintf(f, "\"resolution\": %.17g,\n", res);
+    std::vector<double> idx, cnt;
+    for (const auto& kv : ndt.cells().getLeaves()) { idx.push_back((double)kv.first); cnt.push_back((double)kv.second.nr_points); }
+    put(f, "leaf_idx", idx.data(), idx.size());
+    put(f, "leaf_n", cnt.data(), cnt.size());
+    const Eigen::Vector3i mn = ndt.cells().getMinBoxCoordinates(), mx = ndt.cells().getMaxBoxCoordinates();
+    const double mnv[3] = {(double)mn(0), (double)mn(1), (double)mn(2)}, mxv[3] = {(double)mx(0), (double)mx(1), (double)mx(2)};
+    put(f, "min_b", mnv, 3);
+    put(f, "max_b", mxv, 3);
+    const std::vector<double> kd = ndt.kd_cloud();
+    put(f, "kd_cloud", kd.data(), kd.size());
+    const pclomp::NeighborSearchMethod methods[2] = {pclomp::DIRECT7, pclomp::KDTREE};
+    const char* tags[2] = {"d7", "kdtree"};
+    for (int m = 0; m < 2; m++) {
+      configure(ndt, res, 0.01, 35);
+      ndt.setNeighborhoodSearchMethod(methods[m]);
+      ndt.align(aligned, Eigen::Matrix4f::Identity());
+      const std::string t = tags[m];
+      put(f, ("final_" + t).c_str(), ndt.getFinalTransformation().data(), 16);
+      std::fprintf(f, "\"iters_%s\": %d,\n", tags[m], ndt.getFinalNumIteration());
+      std::vector<double> sc, gr, he;
+      for (std::size_t q = 0; q + 6 <= poses.size(); q += 6) {
+        Eigen::Matrix<double, 6, 1> p, g;
+        Eigen::Matrix<double, 6, 6> H;
+        for (int k = 0; k < 6; k++) p(k) = poses[q + k];
+        sc.push_back(ndt.derivatives(p, g, H));
+        for (int k = 0; k < 6; k++) gr.push_back(g(k));
+        for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) he.push_back(H(r, c));
+      }
+      put(f, ("score_" + t).c_str(), sc.data(), sc.size());
+      put(f, ("grad_" + t).c_str(), gr.data(), gr.size());
+      put(f, ("hess_" + t).c_str(), he.data(), he.size(), m == 1);
+    }
+    std::fprintf(f, "},\n");
   }
   {  // ---- gicp_small (tests/golden/make_golden_gicp.py): target re-filtered like the GICP frontend (scanmatcher_component.cpp:309-315)
     const size_t at = J.find_key("gicp_small", 0);

@@ -13,7 +13,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from lidarslam_ros2_amd import synth  # noqa: E402
+import degenerate_scene  # noqa: E402
 
 
 def write_pcd(path, xyz):
@@ -42,6 +44,12 @@ def main():
     cases["ndt_small"] = {"target": "ndt_small_target.pcd", "source": "ndt_small_source.pcd", "resolution": float(g["res"]),
                           "guess_colmajor": np.asarray(c.guess, np.float32).T.reshape(-1).tolist(), "p": np.asarray(g["p"], np.float64).tolist(),
                           "schedules": [{"name": "eps001", "eps": 0.01, "max_iterations": 35}, {"name": "tight", "eps": 1e-6, "max_iterations": 30}]}
+    # the degenerate-voxel scene (tests/test_degenerate_cpu.py): its poses are the ones the tests evaluate at
+    ds = degenerate_scene.make()
+    write_pcd(os.path.join(a.out, "ndt_degenerate_target.pcd"), ds.target)
+    write_pcd(os.path.join(a.out, "ndt_degenerate_source.pcd"), ds.source)
+    cases["ndt_degenerate"] = {"target": "ndt_degenerate_target.pcd", "source": "ndt_degenerate_source.pcd", "resolution": degenerate_scene.RES,
+                               "poses": np.concatenate([ds.truth + d for d in degenerate_scene.POSES]).tolist()}
     gg = np.load(os.path.join(ROOT, "tests", "golden", "gicp_small_golden.npz"))
     cg = synth.small_case(n_source=int(gg["n_source"]), n_keyframes=int(gg["n_keyframes"]))
     write_pcd(os.path.join(a.out, "gicp_small_target_raw.pcd"), cg.target)

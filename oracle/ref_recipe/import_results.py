@@ -14,6 +14,24 @@ def mat(v):
     return np.asarray(v, np.float64).reshape(4, 4).T.copy()
 
 
+def leaf_centroids_from_kd_cloud(kd_cloud, leaf_idx, min_b, max_b, resolution):
+    """The kd-tree's cloud (VoxelGridCovariance::getCentroids(), leaf-map order) -> (L, 3) float32 per leaf of leaf_idx, NaN for the
+    leaves the cloud does not hold.  Every point lies in its own leaf's cell (a centroid of points of a cell); it is placed there by
+    PCL's fp32 leaf index, and no two points may share a leaf."""
+    kd = np.asarray(kd_cloud, np.float32).reshape(-1, 3)
+    mn, mx = np.asarray(min_b, np.int64), np.asarray(max_b, np.int64)
+    div = mx - mn + 1
+    inv = np.float32(1.0) / np.float32(resolution)
+    key = (np.floor(kd * inv).astype(np.int64) - mn) @ np.array([1, div[0], div[0] * div[1]], np.int64)
+    leaf_idx = np.asarray(leaf_idx, np.int64)
+    pos = np.searchsorted(leaf_idx, key)
+    assert (pos < len(leaf_idx)).all() and (leaf_idx[np.minimum(pos, len(leaf_idx) - 1)] == key).all(), "a kd-tree point outside every leaf"
+    assert len(np.unique(pos)) == len(pos), "two kd-tree points in one leaf"
+    out = np.full((len(leaf_idx), 3), np.nan, np.float32)
+    out[pos] = kd
+    return out
+
+
 def main(path=None, out_dir=None):
     path = path or os.path.join(ROOT, "oracle", "_ref", "out", "results.json")
     out_dir = out_dir or os.path.join(ROOT, "tests", "golden")
@@ -25,9 +43,12 @@ def main(path=None, out_dir=None):
         if "score_kdtree" in n:   # round 6: the KDTREE neighbourhood (dumps made by an older recipe do not hold it: the oracle's arrays stay)
             kd = dict(score_kdtree=float(n["score_kdtree"]), grad_kdtree=np.asarray(n["grad_kdtree"], np.float64),
                       hess_kdtree=np.asarray(n["hess_kdtree"], np.float64).reshape(6, 6), final_kdtree=mat(n["final_kdtree"]).astype(np.float32),
-                      iters_kdtree=int(n["iters_kdtree"]),
-                      leaf_centroid=np.where(np.asarray(n["leaf_centroid"], np.float64) > 1e299, np.nan,
-                                             np.asarray(n["leaf_centroid"], np.float64)).astype(np.float32).reshape(-1, 3))
+                      iters_kdtree=int(n["iters_kdtree"]))
+            if "kd_cloud" in n:   # the kd-tree's own cloud: which leaves are in the tree is read from it, not from nr_points
+                kd["leaf_centroid"] = leaf_centroids_from_kd_cloud(n["kd_cloud"], n["leaf_idx"], n["min_b"], n["max_b"], n["resolution"])
+            else:
+                kd["leaf_centroid"] = np.where(np.asarray(n["leaf_centroid"], np.float64) > 1e299, np.nan,
+                                               np.asarray(n["leaf_centroid"], np.float64)).astype(np.float32).reshape(-1, 3)
         np.savez_compressed(os.path.join(out_dir, "ref_ndt_small_golden.npz"), **kd,
                             score=float(n["score"]), grad=np.asarray(n["grad"], np.float64), hess=np.asarray(n["hess"], np.float64).reshape(6, 6),
                             final_eps001=mat(n["final_eps001"]).astype(np.float32), iters_eps001=int(n["iters_eps001"]),
@@ -35,6 +56,20 @@ def main(path=None, out_dir=None):
                             leaf_idx=np.asarray(n["leaf_idx"], np.int32), leaf_n=np.asarray(n["leaf_n"], np.int32),
                             min_b=np.asarray(n["min_b"], np.int32), max_b=np.asarray(n["max_b"], np.int32))
         wrote.append("ref_ndt_small_golden.npz")
+    if "ndt_degenerate" in R:
+        n = R["ndt_degenerate"]
+        arrs = dict(resolution=float(n["resolution"]), leaf_idx=np.asarray(n["leaf_idx"], np.int32), leaf_n=np.asarray(n["leaf_n"], np.int32),
+                    min_b=np.asarray(n["min_b"], np.int32), max_b=np.asarray(n["max_b"], np.int32),
+                    kd_cloud=np.asarray(n["kd_cloud"], np.float32).reshape(-1, 3),
+                    leaf_centroid=leaf_centroids_from_kd_cloud(n["kd_cloud"], n["leaf_idx"], n["min_b"], n["max_b"], n["resolution"]))
+        for t in ("d7", "kdtree"):
+            arrs["score_" + t] = np.asarray(n["score_" + t], np.float64)
+            arrs["grad_" + t] = np.asarray(n["grad_" + t], np.float64).reshape(-1, 6)
+            arrs["hess_" + t] = np.asarray(n["hess_" + t], np.float64).reshape(-1, 6, 6)
+            arrs["final_" + t] = mat(n["final_" + t])
+            arrs["iters_" + t] = int(n["iters_" + t])
+        np.savez_compressed(os.path.join(out_dir, "ref_ndt_degenerate.npz"), **arrs)
+        wrote.append("ref_ndt_degenerate.npz")
     if "gicp_small" in R:
         g = R["gicp_small"]
         np.savez_compressed(os.path.join(out_dir, "ref_gicp_small_golden.npz"),

@@ -9,9 +9,12 @@ template <typename PointT> class VoxelGridCovariance : public pcl::VoxelGrid<Poi
  public:
   struct FloatVec { float v[4] = {0, 0, 0, 0}; float operator[](int k) const { return v[k]; } };   // Eigen::VectorXf centroid
   struct Leaf { int nr_points = 0; Eigen::Matrix3d cov_, icov_; FloatVec centroid; };
+  using PointCloudPtr = typename pcl::PointCloud<PointT>::Ptr;
   const std::map<std::size_t, Leaf>& getLeaves() const { return leaves_; }
+  PointCloudPtr getCentroids() { return voxel_centroids_; }   // the cloud the KDTREE neighbourhood's kd-tree is built on
  protected:
   std::map<std::size_t, Leaf> leaves_;
+  PointCloudPtr voxel_centroids_;
 };
 template <typename PointSource, typename PointTarget>
 class NormalDistributionsTransform : public pcl::Registration<PointSource, PointTarget> {

@@ -444,6 +444,9 @@ def test_reference_dumper_is_well_formed():
     # and the import step turns them into the files tests/golden_fixtures.py:load_reference() looks for
     src = open(os.path.join(rec, "dump_fixtures.cpp")).read()
     assert '"frontend_stream"' in src.replace("\\", "") and '"loop_gate"' in src.replace("\\", "")
+    # the degenerate-voxel scene is exported and dumped, and kd-tree membership comes from the tree's own cloud (getCentroids())
+    assert '"ndt_degenerate"' in src.replace("\\", "") and "getCentroids()" in src and "nr_points >= 6" not in src
+    assert '"ndt_degenerate"' in open(os.path.join(rec, "export_inputs.py")).read()
     import importlib.util
     import json
     import tempfile
@@ -453,11 +456,28 @@ def test_reference_dumper_is_well_formed():
     eye = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 2.5, 0, 0, 1]   # column-major, x = 2.5
     fake = {"frontend_stream": {"scans": [{"final": eye, "iterations": 6, "points_kept": 100}, {"final": eye, "iterations": 7, "points_kept": 90}], "update_at": [1]},
             "loop_gate": {"pair_id": [1, 20], "final": eye, "fitness": 0.1, "accepted": 1, "n_target_points": 1234, "iterations": 5}}
+    # a degenerate-scene dump shaped like the reference's: the kd-tree cloud holds the in-tree leaves in leaf-map order
+    import degenerate_scene as DS
+    from ndt_numpy import NumpyGrid
+    G = NumpyGrid(DS.make().target, DS.RES)
+    npose = len(DS.POSES)
+    fake["ndt_degenerate"] = dict(resolution=DS.RES, leaf_idx=G.idx.tolist(), leaf_n=G.n.tolist(), min_b=G.min_b.tolist(), max_b=G.max_b.tolist(),
+                                  kd_cloud=G.centroid[G.in_tree].astype(np.float64).ravel().tolist())
+    for t in ("d7", "kdtree"):
+        fake["ndt_degenerate"].update({"score_" + t: [1.0] * npose, "grad_" + t: [0.5] * (6 * npose), "hess_" + t: [0.25] * (36 * npose),
+                                       "final_" + t: eye, "iters_" + t: 4})
     with tempfile.TemporaryDirectory() as d:
         with open(os.path.join(d, "results.json"), "w") as f:
             json.dump(fake, f)
         wrote = imp.main(os.path.join(d, "results.json"), d)
-        assert "ref_frontend_stream.npz" in wrote and "ref_loop_gate.npz" in wrote
+        assert "ref_frontend_stream.npz" in wrote and "ref_loop_gate.npz" in wrote and "ref_ndt_degenerate.npz" in wrote
+        dg = np.load(os.path.join(d, "ref_ndt_degenerate.npz"))
+        # each kd-tree point is placed in its own leaf: the "point" leaves (n = -1) get their centroid, the 5-point leaf stays NaN
+        assert np.array_equal(~np.isnan(dg["leaf_centroid"][:, 0]), G.in_tree) and (dg["leaf_n"] == -1).sum() >= 8
+        assert np.array_equal(dg["leaf_centroid"][G.in_tree], G.centroid[G.in_tree])
+        assert dg["grad_kdtree"].shape == (npose, 6) and dg["hess_d7"].shape == (npose, 6, 6) and dg["final_d7"][0, 3] == 2.5
+        with pytest.raises(AssertionError):   # two tree points in one leaf cannot be placed
+            imp.leaf_centroids_from_kd_cloud(np.repeat(G.centroid[:1], 2, 0).ravel(), G.idx, G.min_b, G.max_b, DS.RES)
         os.environ["LSR_GOLDEN_DIR"] = d
         try:
             sys.path.insert(0, os.path.join(ROOT, "tests"))

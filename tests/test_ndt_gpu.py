@@ -8,8 +8,8 @@ from lidarslam_ros2_amd.posemath import pose_delta
 
 pytestmark = pytest.mark.gpu
 
-POSE_T_TOL = 1e-3   # metres   (north_star)
-POSE_R_TOL = 1e-4   # radians  (north_star)
+from ndt_variants import POSE_R_TOL, POSE_T_TOL, VARIANTS  # noqa: F401  (tolerances: north_star)
+from ndt_variants import tune as _tune
 
 
 @pytest.fixture(scope="module")
@@ -246,17 +246,7 @@ def test_gpu_matches_the_committed_golden_fixture():
     assert dt <= POSE_T_TOL and ang <= POSE_R_TOL and ndt.getFinalNumIteration() == int(gold["iters_kdtree"])
 
 
-# ---- launch variants of the derivative pass and the two grid builders -----------------------------------------------
-# (quad: 1 = four lanes per point (workgroup = points per workgroup: 0 auto / 64 / 128), 0 = lane kernel, one lane per point
-#  (workgroup = threads: 512 / 1024); table mode: 0 dense global, 1 compact global, 2 LDS)
-#  a fourth entry: split = 1 — two waves per chunk in the 512-thread lane kernel (round 6)
-VARIANTS = [(1, 0, 2), (1, 0, 0), (1, 0, 1), (1, 64, 2), (0, 1024, 0), (0, 1024, 1), (0, 1024, 2), (0, 512, 0), (0, 512, 2),
-            (0, 512, 0, 1), (0, 512, 1, 1), (0, 512, 2, 1)]
-
-
-def _tune(ndt, v):
-    quad, workgroup, table_mode = v[:3]
-    ndt.setTuning(workgroup=workgroup, table_mode=table_mode, quad=quad, split=(v[3] if len(v) > 3 else 0))
+# ---- launch variants of the derivative pass and the two grid builders (tests/ndt_variants.py: VARIANTS) ----------------
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
