@@ -140,14 +140,13 @@ int device_cus(int device) {
 constexpr int NDT_QUAD_BATCH_MAX = 1;
 constexpr int NDT_LANE_SINGLE_MIN = 65536;   // source points from which a single registration uses the lane kernel
 int ndt_resident_wgs(int device, int threads) {
-  static const int wgs_per_cu = [] { const char* e = std::getenv("LSR_NDT_WGS_PER_CU"); const int v = e ? std::atoi(e) : 0; return (v >= 1 && v <= 8) ? v : 0; }();
   // two 512-thread workgroups per CU (128 VGPRs per lane: four waves per SIMD; the lane kernel's LDS table + staging tiles fit twice),
   // one of 1024 threads.  (Until round 5 this returned 2048 / threads = 4 for 512: more workgroups than are ever co-resident, each of
   // them paying the head.  Measured on the 64-candidate chain: 1.46 ms with 4, 1.46 ms with 2, 2.04 ms with 1.)
   // Below 512 threads (the quad kernel with 64 points per workgroup: 256 threads, LSR_NDT_WORKGROUP=64) occupancy decides again:
   // 2048 / threads workgroups fill the same four waves per SIMD (the measurement above covers 512 and 1024 only).
   const int by_size = threads >= 1024 ? 1 : threads >= 512 ? 2 : 2048 / std::max(64, threads);
-  return device_cus(device) * (wgs_per_cu ? wgs_per_cu : by_size);
+  return device_cus(device) * by_size;
 }
 int ndt_nblocks(size_t n, int device, int batch, int threads, int points) {
   int nb = (int)((n + points - 1) / points);
@@ -222,13 +221,11 @@ void choose_table_mode(lsr_handle lead, lsr_handle* hs, int B, NdtLaunchCfg& cfg
   // four lanes per point for ONE registration (latency: a 30k-point scan on every CU); the lane kernel for candidate sets and
   // on request (LSR_NDT_QUAD = 0) — both return the same bits, so the choice is a matter of speed only.  Measured on cfg-4 sets of
   // 8 / 16 / 64 candidates (align stage, round 3's kernels): one lane per point 0.61 / 0.90 / 2.73 ms, four lanes 0.76 / 1.09 / 4.06 ms
-  // (env LSR_NDT_QUAD_BATCH_MAX raises the batch size up to which the four-lane kernel is used; read once)
-  static const int quad_batch_max = [] { const char* e = std::getenv("LSR_NDT_QUAD_BATCH_MAX"); const int v = e ? std::atoi(e) : NDT_QUAD_BATCH_MAX; return v < 1 ? 1 : v; }();
   // ... and a single scan large enough to fill the chip with one lane per point takes the lane kernel too: cfg 5 (120k points,
   // dense global table) 9.4 us per pass with 512-thread workgroups against 16.1 us through the quad kernel (round 4)
   size_t n_max = 0;
   for (int b = 0; b < B; b++) n_max = std::max(n_max, hs[b]->source.n);
-  const bool want_quad_single = (B <= quad_batch_max && (lead->ndt_quad == 1 || (lead->ndt_quad < 0 && n_max < (size_t)NDT_LANE_SINGLE_MIN)));
+  const bool want_quad_single = (B <= NDT_QUAD_BATCH_MAX && (lead->ndt_quad == 1 || (lead->ndt_quad < 0 && n_max < (size_t)NDT_LANE_SINGLE_MIN)));
   // 512 threads per workgroup (1024 on request).  A workgroup's waves share ONE compute unit: 1024 threads are four waves per SIMD
   // whatever the size of the set, 512 are two and twice the workgroups — cfg-4 sets of 4 / 8 / 16 / 64 members, align stage:
   // 0.48 / 0.50 / 0.71 / 1.98 ms with 1024 threads, 0.40 / 0.48 / 0.65 / 1.74 ms with 512 (two chains from 6 members on).
@@ -323,25 +320,7 @@ int ensure_ndt_grid(lsr_handle h) {
 
 // An NDT target whose voxel grid was built by the counting-sort builder keeps its points in voxel order: the neighbour grid is
 // a refinement of that order (one launch, nn_build_hash_from_grids) instead of a second sort of the cloud.
-// A/B switch (env LSR_NN_PREFETCH=0: the neighbour grids of a candidate set are built by getFitnessScore, not under the align chain)
-bool nn_prefetch_enabled() {
-  static const bool on = [] { const char* e = getenv("LSR_NN_PREFETCH"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// A/B switch (env LSR_NDT_WIDEN=0: the launches of a candidate set keep their first geometry)
-bool lane_widen_enabled() {
-  static const bool on = [] { const char* e = getenv("LSR_NDT_WIDEN"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// A/B switch (env LSR_NN_FROM_GRID=0: always build the neighbour grid from the cloud); read once
-bool hash_from_grid_enabled() {
-  static const bool enabled = [] { const char* e = getenv("LSR_NN_FROM_GRID"); return !(e && e[0] == '0'); }();
-  return enabled;
-}
 bool hash_from_grid_possible(lsr_handle h) {
-  if (!hash_from_grid_enabled()) return false;
   const TargetData& t = *h->target;
   return h->method == LSR_METHOD_NDT && t.has_grid && t.grid.has_sorted && t.grid.ncells > 0 && t.grid.sorted_n == t.cloud.n;
 }
@@ -435,22 +414,6 @@ int ensure_aux_streams(lsr_handle lead) {
     return LSR_ERR_HIP;
   };
   size_t k = 0;
-  // LSR_SIDE_CUS = K (experiment, VERDICT r05 #2 ii): the side stream — grid refinement, fitness searches of early finishers — is
-  // confined to K compute units (hipExtStreamCreateWithCUMask: the first K bits of the mask; the driver deals the bits of a mask to the
-  // XCDs in turn, so K / 8 CUs of every XCD), the launch chain keeps the rest of the chip to itself
-  static const int side_cus = [] { const char* e = std::getenv("LSR_SIDE_CUS"); return e ? std::atoi(e) : 0; }();
-  if (side_cus > 0) {
-    const int total = device_cus(lead->device);
-    const int words = (total + 31) / 32;
-    std::vector<uint32_t> mask((size_t)words, 0u);
-    for (int c = 0; c < std::min(side_cus, total); c++) mask[c / 32] |= 1u << (c % 32);
-    hipStream_t s = nullptr;
-    if (hipExtStreamCreateWithCUMask(&s, (uint32_t)words, mask.data()) != hipSuccess) return give_up("CU-masked side stream");
-    lead->side_stream = s;
-    if (std::getenv("LSR_DEBUG_STREAMS")) {
-      fprintf(stderr, "[lidarslam_reg] side stream confined to %d of %d CUs\n", std::min(side_cus, total), total);
-    }
-  } else
   if (!found.empty()) lead->side_stream = found[k++];
   else if (hipStreamCreateWithFlags(&lead->side_stream, hipStreamNonBlocking) != hipSuccess) return give_up("no side stream");
   lead->n_chain_streams = 0;
@@ -702,7 +665,7 @@ int align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* finals, 
   // getFitnessScore needs are refined from the voxel order NOW, on a side stream, under the launch chain — the chain is a
   // sequence of short dependent launches that does not fill the chip, the refinement is one wide launch per 16 targets.
   bool prefetched = false;
-  if (B > 1 && nn_prefetch_enabled()) {
+  if (B > 1) {
     std::vector<const VoxelGridDev*> vgs;
     std::vector<HashGridDev*> hgs;
     std::vector<lsr_handle> owners;
@@ -727,7 +690,7 @@ int align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* finals, 
   std::vector<char> eager_ok((size_t)B, 0), eager_queued((size_t)B, 0), eager_sent((size_t)B, 0);   // eligible / finished and waiting for a group / search enqueued
   std::vector<int> eager_ready;
   bool eager = false;
-  if (fitness_out && B > 1 && nn_prefetch_enabled()) {
+  if (fitness_out && B > 1) {
     for (int b = 0; b < B; b++) {
       lsr_handle h = hs[b];
       bool twice = false;
@@ -751,9 +714,9 @@ int align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* finals, 
     // and the grid refinement to 256 / 512 / 1024 resident workgroups (stride loops) so that the chain always finds its slots made it
     // worse still — 1.22 / 0.99 / 0.78 ms against 0.68 for the first share: refinement + searches are ~0.4 ms of full-chip work, at a
     // fraction of the chip they outlast the 0.5 ms chain and the tail is paid at the reduced rate.)
-    static const size_t group_min = [] { const char* e = std::getenv("LSR_FIT_GROUP_MIN"); const int v = e ? std::atoi(e) : 12; return (size_t)std::max(1, std::min(12, v)); }();
-    while (!eager_ready.empty() && (all || eager_ready.size() >= group_min)) {
-      const int n = (int)std::min<size_t>(12, eager_ready.size());
+    constexpr size_t group = 12;
+    while (!eager_ready.empty() && (all || eager_ready.size() >= group)) {
+      const int n = (int)std::min(group, eager_ready.size());
       std::vector<FitJob> jobs;
       for (int k = 0; k < n; k++) {
         const int b = eager_ready[k];
@@ -769,7 +732,7 @@ int align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* finals, 
   const std::function<int()> poll_hook = [&]() { return eager_dispatch(false); };
   int launches = 0;
   st = run_ndt_feeder(lead, lead->d_prob.p, lead->h_prob.p, cfg, min_evals, hard_cap, token, &launches, eager ? &poll_hook : nullptr,
-                      (!cfg.quad && lane_widen_enabled()) ? nb_full : 0, n_chains, chain_first, chain_streams);
+                      !cfg.quad ? nb_full : 0, n_chains, chain_first, chain_streams);
   // whatever follows on the lead's stream (the next align's uploads, a release of the banks) stays behind the chains' queued launches
   if (!chain_join.join() && !st) { set_last_error("joining a launch chain failed"); st = LSR_ERR_HIP; }
   if (eager && !st) st = eager_dispatch(true);
@@ -1052,8 +1015,10 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
 
 static int set_target_impl(lsr_handle h, const void* pts, size_t stride, size_t n, bool on_device) {
   LSR_CHECK_HANDLE(h);
-  if (h->method == LSR_METHOD_NDT && !h->scratch.force_sort_path) {
-    // a set of one: de-interleave and bounding box in one launch, the same counting-sort kernels (661k-point submap: 104 -> 94 us)
+  if (h->method == LSR_METHOD_NDT) {
+    // pclomp::NDT::setInputTarget -> init(): the voxel-covariance grid is built right here, as a set of one — de-interleave and
+    // bounding box in one launch, the group kernels of a candidate set (661k-point submap: 104 -> 94 us); grid_builder = 1 takes the
+    // general builder from there (ndt_grid_geometry)
     lsr_handle one[1] = {h};
     const void* cloud[1] = {pts};
     const size_t count[1] = {n};
@@ -1064,16 +1029,10 @@ static int set_target_impl(lsr_handle h, const void* pts, size_t stride, size_t 
   if (st) return st;
   t->n = n;
   h->target = t;
-  if (h->method == LSR_METHOD_NDT) {
-    // pclomp::NDT::setInputTarget -> init(): the voxel-covariance grid is built right here.
-    st = ensure_ndt_grid(h);
-    if (st) { h->target.reset(); return st; }
-  } else {
-    // GICP: target covariances are computed lazily in align() by the reference; the NN structure is
-    // what setInputTarget pays for (kd-tree there, hash grid here).
-    st = ensure_target_hash(h);
-    if (st) { h->target.reset(); return st; }
-  }
+  // GICP: target covariances are computed lazily in align() by the reference; the NN structure is
+  // what setInputTarget pays for (kd-tree there, hash grid here).
+  st = ensure_target_hash(h);
+  if (st) { h->target.reset(); return st; }
   LSR_HIP(hipStreamSynchronize(h->stream));
   return LSR_OK;
 }

@@ -138,7 +138,7 @@ struct VoxelGridDev {
   bool dense = false;      // rec[] indexed by cell (dense) or by leaf slot (compact)
   DevBuf<int> cell_slot;   // dense [ncells] -> record slot, -1, or -2 - slot for an invalidated leaf (ndt.hpp: cell_slot_code)
   DevBuf<float4> rec;      // [n_leaves * 4]
-  // LDS image of the valid-voxel table (ndt_pack_lds_table): uint16 cell->slot map (0xFFFF = none) followed by 48-byte
+  // LDS image of the valid-voxel table (ndt_pack_lds_tables): uint16 cell->slot map (0xFFFF = none) followed by 48-byte
   // records of the usable leaves; lds_bytes == 0 when the table is too large to stage
   DevBuf<uint4> lds_image;
   int lds_map_bytes = 0, lds_bytes = 0;

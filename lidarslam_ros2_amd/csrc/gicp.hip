@@ -34,11 +34,7 @@ static bool gicp_fused_enabled() {
 // Largest ball (fine cells per axis, 3..8: an x-range of <= 8 cells touches at most two coarse cells) the seeded correspondence
 // kernel searches itself; larger ones go to the general search, which costs a wave per point and a long chain of dependent
 // probes: measured on cfg 3 (setInputSource + align) 3 cells 0.834 ms, 5 cells 0.734, 7 cells 0.739, 8 cells 0.750.
-// env LSR_GICP_BALL_CELLS, read once.
-static int gicp_ball_cells() {
-  static const int v = [] { const char* e = getenv("LSR_GICP_BALL_CELLS"); const int c = e ? atoi(e) : 5; return c < 3 ? 3 : c > 8 ? 8 : c; }();
-  return v;
-}
+constexpr int GICP_BALL_CELLS = 5;
 
 namespace {
 
@@ -283,7 +279,7 @@ __global__ __launch_bounds__(256) void gicp_cov_from_nbr_kernel(const float* __r
 
 // The start of an align in ONE launch (round 6; a copy, this kernel and a fill until then: two launches and their gaps less on a chain of
 // short launches): the iteration block travels in the kernel arguments and is written to its device home by workgroup 0, the pair
-// counters / work-list head are zeroed, and output = guess * input as below.
+// counters / work-list head are zeroed, and output = guess * input (fp32, reference order of operations).
 static_assert(sizeof(IterBlock) <= 3072, "IterBlock travels in the kernel arguments (4 KiB limit)");
 __global__ __launch_bounds__(256) void gicp_begin_align_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n,
                                                                const IterBlock blk, IterBlock* __restrict__ d_blk, int* __restrict__ zero_words, int n_zero,
@@ -297,18 +293,6 @@ __global__ __launch_bounds__(256) void gicp_begin_align_kernel(const float* __re
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* G16 = blk.out.G;
-  const float a = x[i], b = y[i], c = z[i];
-  ox[i] = xform_rn(G16[0], G16[4], G16[8], G16[12], a, b, c);
-  oy[i] = xform_rn(G16[1], G16[5], G16[9], G16[13], a, b, c);
-  oz[i] = xform_rn(G16[2], G16[6], G16[10], G16[14], a, b, c);
-}
-
-// output = guess * input (fp32, reference order of operations)
-__global__ __launch_bounds__(256) void gicp_apply_guess_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                               const float* __restrict__ z, int n, const float* __restrict__ G16,
-                                                               float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
   const float a = x[i], b = y[i], c = z[i];
   ox[i] = xform_rn(G16[0], G16[4], G16[8], G16[12], a, b, c);
   oy[i] = xform_rn(G16[1], G16[5], G16[9], G16[13], a, b, c);
@@ -1347,13 +1331,13 @@ struct GicpChain {
         {
           hipLaunchKernelGGL(gicp_corr_seeded_kernel, dim3((unsigned)(((long)n * 16 + 255) / 256)), dim3(256), 0, s, make_view(t.hash),
                              ws.out.x(), ws.out.y(), ws.out.z(), n, cur->T16, cur->Rm, thr2, t.cloud.x(), t.cloud.y(), t.cloud.z(),
-                             h->source_cov.p, t.cov.p, &cur->out, ws.last_nn.p, ws.nn_d2.p, d_pairs, d_shards, gicp_ball_cells());
+                             h->source_cov.p, t.cov.p, &cur->out, ws.last_nn.p, ws.nn_d2.p, d_pairs, d_shards, GICP_BALL_CELLS);
         }
       } else {
       if (ball)
         hipLaunchKernelGGL(gicp_corr_ball_kernel, dim3((unsigned)(((long)n * 16 + 255) / 256)), dim3(256), 0, s, make_view(t.hash),
                            ws.out.x(), ws.out.y(), ws.out.z(), n, cur->T16, thr2, t.cloud.x(), t.cloud.y(), t.cloud.z(), &cur->out,
-                           ws.last_nn.p, ws.nn_d2.p, d_work, gicp_ball_cells());
+                           ws.last_nn.p, ws.nn_d2.p, d_work, GICP_BALL_CELLS);
       // the first group is the first outer iteration (every point, one wave each); later groups only run the general search
       // on what the seeded kernel deferred (grid-stride over the list: a small grid, not 7 500 workgroups that exit)
       const unsigned full_grid = (unsigned)(((long)n * 64 + 255) / 256);

@@ -281,19 +281,15 @@ __device__ __forceinline__ void lds_pack_body(const int* __restrict__ cell_slot,
     __hip_atomic_store(&mb->done_token, token, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
-__global__ __launch_bounds__(1024) void lds_pack_kernel(const int* __restrict__ cell_slot, const float4* __restrict__ rec,
-                                                        const int* __restrict__ leaf_n, int ncells, int map_bytes, int image_cap,
-                                                        unsigned char* __restrict__ image, BuildMailbox* __restrict__ mb, unsigned int token) {
-  lds_pack_body(cell_slot, rec, leaf_n, ncells, map_bytes, image_cap, image, mb, token);
-}
-// one workgroup per member of a group of targets (batched builds, grid_dense.hip)
+// one workgroup per member of a group of targets
 __global__ __launch_bounds__(1024) void lds_pack_group_kernel(const PackGroup g) {
   const PackMember& M = g.m[blockIdx.x];
   lds_pack_body(M.cell_slot, M.rec, M.leaf_n, M.ncells, M.map_bytes, M.image_cap, M.image, M.mb, M.token);
 }
 }  // namespace
 
-int ndt_pack_lds_tables(VoxelGridDev* const* grids, BuildScratch* const* scs, const unsigned int* tokens, int count, hipStream_t stream) {
+int ndt_pack_lds_tables(VoxelGridDev* const* grids, BuildScratch* const* scs, const unsigned int* tokens, int count, bool per_cell_leaf_n,
+                        hipStream_t stream) {
   for (int g0 = 0; g0 < count; g0 += LSR_GROUP) {
     PackGroup grp;
     const int ng = std::min(LSR_GROUP, count - g0);
@@ -306,7 +302,7 @@ int ndt_pack_lds_tables(VoxelGridDev* const* grids, BuildScratch* const* scs, co
       const bool may_fit = grid.ncells > 0 && grid.ncells * 2 + 16 + NDT_LDS_REC_BYTES <= (size_t)NDT_LDS_TABLE_MAX;
       if (may_fit && (st = grid.lds_image.reserve(NDT_LDS_TABLE_MAX / 16))) return st;
       PackMember& M = grp.m[k];
-      M.cell_slot = grid.cell_slot.p; M.rec = grid.rec.p; M.leaf_n = grid.leaf_n.p; M.ncells = (int)grid.ncells;
+      M.cell_slot = grid.cell_slot.p; M.rec = grid.rec.p; M.leaf_n = per_cell_leaf_n ? grid.leaf_n.p : nullptr; M.ncells = (int)grid.ncells;
       M.map_bytes = (int)((grid.ncells * 2 + 15) & ~(size_t)15); M.image_cap = (int)NDT_LDS_TABLE_MAX;
       M.image = may_fit ? reinterpret_cast<unsigned char*>(grid.lds_image.p) : (unsigned char*)nullptr;
       M.mb = sc.d_mb; M.token = tokens[g0 + k];
@@ -317,29 +313,16 @@ int ndt_pack_lds_tables(VoxelGridDev* const* grids, BuildScratch* const* scs, co
   return LSR_OK;
 }
 
-// Enqueue the pack; the outcome is read from the host mailbox by ndt_finish_grid().
-int ndt_pack_lds_table(VoxelGridDev& grid, BuildScratch& sc, bool per_cell_leaf_n, unsigned int token, hipStream_t stream) {
-  grid.lds_bytes = grid.lds_map_bytes = 0;
-  int st = sc.ensure_mailbox();
-  if (st) return st;
-  const bool may_fit = grid.ncells > 0 && grid.ncells * 2 + 16 + NDT_LDS_REC_BYTES <= (size_t)NDT_LDS_TABLE_MAX;
-  const int map_bytes = (int)((grid.ncells * 2 + 15) & ~(size_t)15);
-  if (may_fit && (st = grid.lds_image.reserve(NDT_LDS_TABLE_MAX / 16))) return st;
-  hipLaunchKernelGGL(lds_pack_kernel, dim3(1), dim3(1024), 0, stream, grid.cell_slot.p, grid.rec.p,
-                     per_cell_leaf_n ? grid.leaf_n.p : (const int*)nullptr, (int)grid.ncells, map_bytes, (int)NDT_LDS_TABLE_MAX,
-                     may_fit ? reinterpret_cast<unsigned char*>(grid.lds_image.p) : (unsigned char*)nullptr, sc.d_mb, token);
-  LSR_HIP(hipGetLastError());
-  return LSR_OK;
-}
-
-int ndt_build_grid(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream) {
+// A single target is a set of one.  Its cloud is in place already, so the job carries no strided records (only the ingest reads them).
+int ndt_build_grid(DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream) {
   int st = cloud_bbox_begin(cloud, sc, stream);
   if (st) return st;
-  if ((st = ndt_build_grid_begin(cloud, leaf, grid, sc, stream))) return st;
+  TargetBuildJob job{nullptr, 0, cloud.n, &cloud, leaf, &grid, &sc, 0};
+  if ((st = ndt_targets_build_begin(&job, 1, stream))) return st;
   return ndt_build_grid_end(grid, sc, stream);
 }
 
-// Collect a build left pending by ndt_build_grid_begin (host poll #2).
+// Collect a build left pending by ndt_targets_build_begin (host poll #2).
 int ndt_build_grid_end(VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream) {
   if (!sc.grid_pending) return LSR_OK;
   sc.grid_pending = false;
@@ -477,7 +460,9 @@ static int ndt_build_grid_general(const DeviceCloud& cloud, float leaf, VoxelGri
                      6, 0.01, grid.rec.p, grid.mean64.p, grid.icov64.p, grid.leaf_key.p, grid.leaf_n.p, grid.cell_slot.p,
                      d_nvalid, grid.dense ? 1 : 0, sentinel, n_runs_dev);
   LSR_HIP(hipGetLastError());
-  if ((st = ndt_pack_lds_table(grid, sc, false, token, stream))) return st;
+  VoxelGridDev* grids[1] = {&grid};
+  BuildScratch* scs[1] = {&sc};
+  if ((st = ndt_pack_lds_tables(grids, scs, &token, 1, false, stream))) return st;   // leaf_n is indexed by run here, not by cell
   if ((st = wait_mailbox_word(&sc.mb.p->done_token, token, stream, sc.wait_mode, "voxel grid build"))) return st;
   if (n_runs_dev && (st = sorted_runs_count(sc, stream, rtoken, &n_runs))) return st;   // published long before the pack: no wait
   grid.n_leaves = n_runs;  // includes the sentinel run if non-finite points exist (leaf_key = -1)
@@ -556,21 +541,6 @@ int ndt_build_centroids(const DeviceCloud& cloud, VoxelGridDev& grid, BuildScrat
   return LSR_OK;
 }
 
-// Everything up to the last enqueue.  Dense key spaces leave the build pending (sc.grid_pending): ndt_build_grid_end() collects it.
-int ndt_build_grid_begin(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream) {
-  int path = 0;
-  int st = ndt_grid_geometry(cloud, leaf, grid, sc, stream, &path);
-  if (st || path == 0) return st;
-  if (path == 2) return ndt_build_grid_general(cloud, leaf, grid, sc, stream);
-  // dense key space: hand-written counting sort, no further host round trip until the final poll (grid_dense.hip)
-  const unsigned int token = next_token(sc);
-  if ((st = ndt_build_grid_dense(cloud, leaf, grid, sc, stream))) return st;
-  if ((st = ndt_pack_lds_table(grid, sc, true, token, stream))) return st;
-  sc.grid_pending = true;
-  sc.grid_token = token;
-  return LSR_OK;
-}
-
 // A SET of targets (candidate windows): every member's bounding box has been enqueued (ndt_targets_ingest / cloud_bbox_begin).
 // Members with a dense key space are built by the GROUP kernels of grid_dense.hip — one launch per stage for up to LSR_GROUP
 // members — and left pending; the others are built one by one right here.
@@ -597,7 +567,7 @@ int ndt_targets_build_begin(TargetBuildJob* jobs, int count, hipStream_t stream)
       tokens.push_back(next_token(*J->sc));
     }
     if ((st = ndt_build_grids_dense_group(dense.data(), (int)dense.size(), stream))) return st;
-    if ((st = ndt_pack_lds_tables(grids.data(), scs.data(), tokens.data(), (int)dense.size(), stream))) return st;
+    if ((st = ndt_pack_lds_tables(grids.data(), scs.data(), tokens.data(), (int)dense.size(), true, stream))) return st;
     for (size_t k = 0; k < dense.size(); k++) { dense[k]->sc->grid_pending = true; dense[k]->sc->grid_token = tokens[k]; }
   }
   for (int b = 0; b < count; b++)

@@ -12,8 +12,8 @@
 //   vg_leaf            one workgroup per cell: fp64 sums in a fixed order + leaf finalisation (K2)   reads 12 B/pt
 //   lds_pack           LDS image of the usable leaves, counts into the host mailbox (ndt.hip)
 //
-// Every stage exists as a body + a single-target kernel + a GROUP kernel (up to LSR_GROUP = 16 targets per launch, the
-// members' pointers and sizes in the kernel arguments, blockIdx.y = member): a candidate set pays one launch per stage per
+// Every stage is a body run by a GROUP kernel (up to LSR_GROUP = 16 targets per launch, the members' pointers and sizes in
+// the kernel arguments, blockIdx.y = member; a single target is a group of one): a candidate set pays one launch per stage per
 // 16 targets.  The voxel-ordered points stay with the grid (sorted planes, sorted_idx, cell_start, cell_rank): the
 // neighbour grid of getFitnessScore is a refinement of that order (nn.hip).  No device-to-host copy, two host polls (bbox,
 // done) — against ~35 launches and three stream synchronisations of the sort-based builder (which remains for larger key
@@ -121,11 +121,6 @@ __device__ __forceinline__ void vg_hist_kernel_body(const float* __restrict__ x,
   __syncthreads();
   unsigned short* row = hist + (size_t)blk_x * C;
   for (int k = tid; k < C; k += 256) row[k] = (unsigned short)s_hist[k];  // <= VG_CHUNK = 4096
-}
-__global__ __launch_bounds__(256) void vg_hist_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                                                      int n, float inv_leaf, int mb0, int mb1, int mb2, int mul1, int mul2, int ncells,
-                                                      unsigned short* __restrict__ keys, unsigned short* __restrict__ hist) {
-  vg_hist_kernel_body(x, y, z, n, inv_leaf, mb0, mb1, mb2, mul1, mul2, ncells, keys, hist, (int)blockIdx.x);
 }
 
 // per cell: exclusive scan of the block histograms (offset of this block's points inside the cell) + cell total.
@@ -338,14 +333,6 @@ __device__ __forceinline__ void vg_leaf_kernel_body(const float* __restrict__ sx
   leaf_record_dev(mean, icov, n, valid, rec + (size_t)cell * 4);
   cell_slot[cell] = cell_slot_code(valid, n, cell);
 }
-__global__ __launch_bounds__(VG_LEAF_THREADS) void vg_leaf_kernel(const float* __restrict__ sx, const float* __restrict__ sy,
-                                                                  const float* __restrict__ sz, const unsigned int* __restrict__ start,
-                                                                  int ncells, int min_points, double eig_mult, float4* __restrict__ rec,
-                                                                  double* __restrict__ mean64, double* __restrict__ icov64,
-                                                                  int* __restrict__ leaf_key, int* __restrict__ leaf_n,
-                                                                  int* __restrict__ cell_slot) {
-  vg_leaf_kernel_body(sx, sy, sz, start, ncells, min_points, eig_mult, rec, mean64, icov64, leaf_key, leaf_n, cell_slot, (int)blockIdx.x);
-}
 
 // the second half of the SUMS_ONLY form: one thread per cell
 __device__ __forceinline__ void vg_leaf_finish_body(const unsigned int* __restrict__ start, int ncells, int min_points, double eig_mult,
@@ -530,59 +517,6 @@ __global__ __launch_bounds__(256) void src_hist_kernel(const float* __restrict__
 
 }  // namespace
 
-// Everything after the bounding box for a dense key space.  grid.min_b / max_b / div_b / ncells are set by the caller.
-int ndt_build_grid_dense(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream) {
-  const int n = (int)cloud.n;
-  const int ncells = (int)grid.ncells, C = ncells + 1;
-  const int nblk = (n + VG_CHUNK - 1) / VG_CHUNK;
-  const float inv_leaf = 1.0f / leaf;
-  int st;
-  // scratch words: total[C] | blkoff[nblk*C] | hist(u16)[nblk*C] | keys(u16)[n]; the cell-ordered points, their indices, the cell
-  // starts and ranks stay with the grid (the neighbour grid of getFitnessScore refines them)
-  const size_t w_total = (size_t)C, w_blkoff = (size_t)nblk * C, w_hist = ((size_t)nblk * C + 1) / 2, w_keys = ((size_t)n + 1) / 2;
-  if ((st = sc.words.reserve(16 + w_total + w_blkoff + w_hist + w_keys + 16))) return st;
-  unsigned int* total = sc.words.p + 16;
-  unsigned int* blkoff = total + w_total;
-  unsigned short* hist = reinterpret_cast<unsigned short*>(blkoff + w_blkoff);
-  unsigned short* keys = reinterpret_cast<unsigned short*>(blkoff + w_blkoff + w_hist);
-  const size_t pitch = ((size_t)n + 63) & ~(size_t)63;
-  if ((st = grid.sorted.reserve(3 * pitch))) return st;
-  if ((st = grid.sorted_idx.reserve(pitch))) return st;
-  if ((st = grid.cell_start.reserve((size_t)C + 1))) return st;
-  if ((st = grid.cell_rank.reserve((size_t)C))) return st;
-  grid.sorted_pitch = pitch; grid.sorted_n = (size_t)n; grid.has_sorted = true;
-  unsigned int* start = grid.cell_start.p;
-  float* sx = grid.sorted.p; float* sy = sx + pitch; float* sz = sy + pitch;
-  if ((st = grid.cell_slot.reserve(grid.ncells))) return st;
-  if ((st = grid.rec.reserve(grid.ncells * 4))) return st;
-  if ((st = grid.mean64.reserve(grid.ncells * 3))) return st;
-  if ((st = grid.icov64.reserve(grid.ncells * 9))) return st;
-  if ((st = grid.leaf_key.reserve(grid.ncells))) return st;
-  if ((st = grid.leaf_n.reserve(grid.ncells))) return st;
-  grid.dense = true;
-
-  static bool attr_done[64] = {};
-  int dev = 0;
-  LSR_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64 && !attr_done[dev]) {
-    LSR_HIP(hipFuncSetAttribute((const void*)vg_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VG_DENSE_MAX_CELLS * 4 + 4));
-    LSR_HIP(hipFuncSetAttribute((const void*)vg_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VG_DENSE_MAX_CELLS * 8 + 8));
-    attr_done[dev] = true;
-  }
-  const int mul1 = grid.div_b[0], mul2 = grid.div_b[0] * grid.div_b[1];
-  hipLaunchKernelGGL(vg_hist_kernel, dim3(nblk), dim3(256), (size_t)C * 4, stream, cloud.x(), cloud.y(), cloud.z(), n, inv_leaf,
-                       grid.min_b[0], grid.min_b[1], grid.min_b[2], mul1, mul2, ncells, keys, hist);
-  hipLaunchKernelGGL(vg_scan_kernel, dim3((C + 31) / 32), dim3(256), 0, stream, hist, nblk, C, blkoff, total);
-  hipLaunchKernelGGL(vg_cellscan_kernel, dim3(1), dim3(1024), 0, stream, total, C, start, grid.cell_rank.p);
-  hipLaunchKernelGGL(vg_scatter_kernel, dim3(nblk), dim3(256), (size_t)C * 8, stream, cloud.x(), cloud.y(), cloud.z(), n, keys, blkoff,
-                     start, C, sx, sy, sz, grid.sorted_idx.p);
-  hipLaunchKernelGGL(vg_leaf_kernel, dim3((ncells + VG_LEAF_THREADS / 64 - 1) / (VG_LEAF_THREADS / 64)), dim3(VG_LEAF_THREADS), 0, stream, sx, sy, sz, start, ncells, 6, 0.01, grid.rec.p,
-                     grid.mean64.p, grid.icov64.p, grid.leaf_key.p, grid.leaf_n.p, grid.cell_slot.p);
-  LSR_HIP(hipGetLastError());
-  grid.n_leaves = ncells;  // leaf arrays are indexed by cell; empty cells carry leaf_key = -1
-  return LSR_OK;
-}
-
 int ndt_sort_source(const DeviceCloud& src, const float* T12, const VoxelGridDev& grid, DeviceCloud& out, BuildScratch& sc, hipStream_t stream) {
   const int n = (int)src.n;
   int st = out.resize(src.n);
@@ -670,7 +604,8 @@ int ndt_build_grids_dense_group(TargetBuildJob* const* jobs, int count, hipStrea
       const int n = (int)cloud.n;
       const int ncells = (int)grid.ncells, C = ncells + 1;
       const int nblk = (n + VG_CHUNK - 1) / VG_CHUNK;
-      // the same scratch layout as the single-target builder
+      // scratch words: total[C] | blkoff[nblk*C] | hist(u16)[nblk*C] | keys(u16)[n]; the cell-ordered points, their indices, the cell
+      // starts and ranks stay with the grid (the neighbour grid of getFitnessScore refines them)
       const size_t w_total = (size_t)C, w_blkoff = (size_t)nblk * C, w_hist = ((size_t)nblk * C + 1) / 2, w_keys = ((size_t)n + 1) / 2;
       if ((st = sc.words.reserve(16 + w_total + w_blkoff + w_hist + w_keys + 16))) return st;
       const size_t pitch = ((size_t)n + 63) & ~(size_t)63;
@@ -709,9 +644,8 @@ int ndt_build_grids_dense_group(TargetBuildJob* const* jobs, int count, hipStrea
     hipLaunchKernelGGL(vg_scan_group_kernel, dim3((maxC + 31) / 32, ng), dim3(256), 0, stream, grp);
     hipLaunchKernelGGL(vg_cellscan_group_kernel, dim3(ng), dim3(1024), 0, stream, grp);
     hipLaunchKernelGGL(vg_scatter_group_kernel, dim3(max_nblk, ng), dim3(256), (size_t)maxC * 8, stream, grp);
-    // from two targets on: the sums by one wave per cell, the finalisation by one thread per cell in a launch of its own (LSR_VG_LEAF_SPLIT=0 / 1 forces)
-    static const int split_env = [] { const char* e = getenv("LSR_VG_LEAF_SPLIT"); return e ? atoi(e) : -1; }();
-    if (split_env == 1 || (split_env < 0 && ng >= 2)) {
+    // from two targets on: the sums by one wave per cell, the finalisation by one thread per cell in a launch of its own
+    if (ng >= 2) {
       hipLaunchKernelGGL(vg_leaf_sums_group_kernel, dim3((max_cells + VG_LEAF_THREADS / 64 - 1) / (VG_LEAF_THREADS / 64), ng), dim3(VG_LEAF_THREADS), 0, stream, grp);
       hipLaunchKernelGGL(vg_leaf_finish_group_kernel, dim3((max_cells + 255) / 256, ng), dim3(256), 0, stream, grp);
     } else {

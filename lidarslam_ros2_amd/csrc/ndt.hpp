@@ -134,11 +134,11 @@ int cloud_bbox(const DeviceCloud& cloud, float* mn, float* mx, unsigned int* n_f
 int cloud_bbox_begin(const DeviceCloud& cloud, BuildScratch& sc, hipStream_t stream);   // enqueue only
 int cloud_bbox_end(const DeviceCloud& cloud, float* mn, float* mx, unsigned int* n_finite, BuildScratch& sc, hipStream_t stream);
 
-// K1/K2: build grid from the SoA cloud.  Returns once the grid is complete (host polls the build mailbox twice).
-int ndt_build_grid(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream);
-// The same in two halves (after cloud_bbox_begin): _begin waits for the bounding box and enqueues the rest, _end waits for
-// the result.  A batch of targets runs every _begin before the first _end, so the builds overlap on the device.
-int ndt_build_grid_begin(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream);
+// K1/K2: build grid from the SoA cloud, as a set of one target (ndt_targets_build_begin).  Returns once the grid is complete
+// (host polls the build mailbox twice).
+int ndt_build_grid(DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream);
+// Wait for a member's build left pending by ndt_targets_build_begin.  A batch of targets enqueues every build before the
+// first _end, so the builds overlap on the device.
 int ndt_build_grid_end(VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream);
 // KDTREE neighbourhood: grid.centroid of a complete grid (stable sort of the cloud by leaf + one thread per leaf adding its points in
 // cloud order, in float, as VoxelGridCovariance does for Leaf::centroid).  Returns with the array complete.
@@ -165,9 +165,6 @@ constexpr int NDT_QUAD_POINTS = NDT_QUAD_THREADS / 4;  // source points per work
 // h_single (nullable): host copy of the problem, passed by value when batch == 1.
 int ndt_launch_evals(const NdtProblem* d_probs, const NdtProblem* h_single, const NdtLaunchCfg& cfg, int seq0, int count,
                      hipStream_t stream);
-// Enqueue the LDS image of the valid-voxel table (grid.lds_image) after the leaf records exist; the kernel publishes
-// n_valid / lds_bytes (0 when the table does not fit NDT_LDS_TABLE_MAX) and the `token` into the host mailbox.
-int ndt_pack_lds_table(VoxelGridDev& grid, BuildScratch& sc, bool per_cell_leaf_n, unsigned int token, hipStream_t stream);
 // ---- batched builds (candidate sets, graph_based_slam_component.cpp:181-231 generalised): the per-member parameters of up to
 // LSR_GROUP members travel in the kernel arguments of ONE launch whose grid's y (or x) index selects the member.
 constexpr int LSR_GROUP = 16;
@@ -176,8 +173,12 @@ struct PackMember {
   unsigned char* image; BuildMailbox* mb;
 };
 struct PackGroup { PackMember m[LSR_GROUP]; };
-// lds_pack for `count` dense grids (leaf_n per cell) in ceil(count / LSR_GROUP) launches
-int ndt_pack_lds_tables(VoxelGridDev* const* grids, BuildScratch* const* scs, const unsigned int* tokens, int count, hipStream_t stream);
+// Enqueue the LDS image of the valid-voxel table (grid.lds_image) of `count` grids, after their leaf records exist, in
+// ceil(count / LSR_GROUP) launches; each member publishes n_valid / lds_bytes (0 when the table does not fit
+// NDT_LDS_TABLE_MAX) and its token into its host mailbox.  per_cell_leaf_n: grid.leaf_n is indexed by cell (the counting-sort
+// builder), so the occupied cells are counted too.
+int ndt_pack_lds_tables(VoxelGridDev* const* grids, BuildScratch* const* scs, const unsigned int* tokens, int count, bool per_cell_leaf_n,
+                        hipStream_t stream);
 
 // One target of a batched build: device-resident strided records in, SoA cloud + voxel grid out (each member keeps its own
 // scratch and host mailbox).
@@ -193,12 +194,11 @@ int ndt_targets_build_begin(TargetBuildJob* jobs, int count, hipStream_t stream)
 int ndt_build_grids_dense_group(TargetBuildJob* const* jobs, int count, hipStream_t stream);
 int ndt_grid_geometry(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream, int* path);
 
-// K1/K2 for dense key spaces (grid_dense.hip): counting sort + per-cell sums + finalisation, everything enqueued, no host
-// round trip.  grid.min_b / div_b / ncells must be set.
+// K1/K2 for dense key spaces (ndt_build_grids_dense_group, grid_dense.hip): counting sort + per-cell sums + finalisation,
+// everything enqueued, no host round trip.  The members' grid.min_b / div_b / ncells must be set (ndt_grid_geometry).
 constexpr int VG_DENSE_MAX_CELLS = 16383;   // beyond: radix sort.  (A two-wave form with 32-bit packed counters for up to 36 000 cells was
                                             // built and measured on cfg 5's 22 113-cell grid: 0.33-0.35 ms against the radix sort's 0.30 — every
                                             // 4096-point workgroup clears, writes and prefixes a 22k-entry table; removed.)
-int ndt_build_grid_dense(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, BuildScratch& sc, hipStream_t stream);
 // Order the source cloud by voxel tile (NDT_TAB_TILE): counting sort of the points by the Morton code of the 2^shift x 2^shift
 // column of grid cells their guess-moved image falls into (grid_dense.hip).  Consecutive points of `out` are neighbours in
 // space, so the cells a workgroup of the derivative pass touches form a small box.  T12: row-major 3x4 guess (host memory).

@@ -344,22 +344,18 @@ __global__ __launch_bounds__(256) void nn1_wave_kernel(NNGridView G, const float
 // travel in the kernel arguments (no per-member upload of the 4x4)
 struct FitMember {
   NNGridView G;
-  const float *qx, *qy, *qz; int n, blocks;
+  const float *qx, *qy, *qz; int n;
   float T16[16];
   float max_d2; double max_range;
   int* idx; float* d2; double* part; int* work;
-  BuildMailbox* mb; unsigned int token; int empty; int fine_rings;
-  int ball_cells;   // widest ball (fine cells per axis) the sixteen-lane search reads itself; wider ones go to the work list
+  BuildMailbox* mb; unsigned int token; int empty;
 };
 constexpr int FIT_GROUP = 12;
-constexpr int NN_FITNESS_FINE_RINGS = 0;   // measured on 64 candidate windows (fitness stage): 2.54 ms with 1, 2.39 ms with 0
+// Shells the fitness search reads before it tests the shell bound for the first time: 0 lets a query whose own cell already proves
+// its neighbour stop there.  Measured on 64 candidate windows (fitness stage): 2.54 ms with 1, 2.39 ms with 0.
+constexpr int NN_FITNESS_FINE_RINGS = 0;
 struct FitGroup { FitMember m[FIT_GROUP]; };
 static_assert(sizeof(FitGroup) <= 3800, "a group's parameters must fit the kernel argument segment");
-__global__ __launch_bounds__(256) void nn1_wave_group_kernel(const FitGroup g) {
-  const FitMember& M = g.m[blockIdx.y];
-  if ((int)blockIdx.x >= M.blocks || M.empty) return;
-  nn1_wave_body(M.G, M.qx, M.qy, M.qz, M.n, M.T16, M.fine_rings, M.max_d2, M.idx, M.d2, (blockIdx.x * 256 + threadIdx.x) >> 6, (M.blocks * 256) >> 6);
-}
 
 // tail of nn1_kernel: one wave per deferred query; same (distance, index) order, same fp32 distances => same answer
 __device__ __forceinline__ void nn1_coop_body(const NNGridView& G, const float* __restrict__ qx, const float* __restrict__ qy,
@@ -449,9 +445,10 @@ __device__ __forceinline__ void fitness_final_body(const double* __restrict__ pa
 __global__ __launch_bounds__(256) void fitness_final_kernel(const double* __restrict__ part, BuildMailbox* __restrict__ mb, unsigned int token) {
   fitness_final_body(part, mb, token);
 }
-// alternative form (LSR_FIT_GROUP_FORM=1): capped walk on four lanes per query + wave-cooperative tail for the queries it defers —
-// the same answers, and on paper a sixth of the instructions per query once millions of queries fill the chip; measured
-// slower than one wave per query (the deferred tail alone costs as much as it saves)
+// (The group search also existed as one wave per query, and as a capped walk on four lanes per query + a wave-cooperative tail for
+// the queries it defers — on paper a sixth of the instructions per query once millions of queries fill the chip.  Same answers; the
+// four-lane form measured 5.85 ms against 3.54 ms for one wave per query on 64 candidates x 30k queries.  Both gave way to the
+// sixteen-lane ball form below and were removed.)
 __global__ void fit_zero_work_group_kernel(const FitGroup g) { g.m[threadIdx.x].work[0] = 0; }   // empty deferred-query lists
 
 // getFitnessScore's search on SIXTEEN lanes per query, seeded by the query's own fine cell (round 4).
@@ -533,7 +530,7 @@ __global__ __launch_bounds__(256) void nn1_list_group_kernel(const FitGroup g) {
     CoopList mine;
     mine.d = INFINITY;
     mine.i = INT_MAX;
-    coop_search<true>(M.G, tx, ty, tz, 1, M.fine_rings, M.max_d2, -1, mine);
+    coop_search<true>(M.G, tx, ty, tz, 1, NN_FITNESS_FINE_RINGS, M.max_d2, -1, mine);
     if (lane == 0) {
       const bool found = mine.i != INT_MAX;
       M.idx[i] = found ? mine.i : -1;
@@ -544,17 +541,7 @@ __global__ __launch_bounds__(256) void nn1_list_group_kernel(const FitGroup g) {
 __global__ __launch_bounds__(256) void nn1_ball_group_kernel(const FitGroup g) {
   const FitMember& M = g.m[blockIdx.y];
   if (M.empty) return;
-  nn1_ball_body(M.G, M.qx, M.qy, M.qz, M.n, M.T16, M.work, M.idx, M.d2, blockIdx.x * 256 + threadIdx.x, M.ball_cells);
-}
-__global__ __launch_bounds__(NN_THREADS) void nn1_quad_group_kernel(const FitGroup g) {
-  const FitMember& M = g.m[blockIdx.y];
-  if (M.empty) return;
-  nn1_quad_body(M.G, M.qx, M.qy, M.qz, M.n, M.T16, 1, 2, M.max_d2, M.work, M.idx, M.d2, blockIdx.x * NN_THREADS + threadIdx.x);
-}
-__global__ __launch_bounds__(256) void nn1_coop_group_kernel(const FitGroup g) {
-  const FitMember& M = g.m[blockIdx.y];
-  if (M.empty) return;
-  nn1_coop_body(M.G, M.qx, M.qy, M.qz, M.T16, M.max_d2, M.work, M.idx, M.d2, (blockIdx.x * 256 + threadIdx.x) >> 6, (gridDim.x * 256) >> 6);
+  nn1_ball_body(M.G, M.qx, M.qy, M.qz, M.n, M.T16, M.work, M.idx, M.d2, blockIdx.x * 256 + threadIdx.x, FIT_BALL_CELLS);
 }
 __global__ __launch_bounds__(256) void fitness_partial_group_kernel(const FitGroup g) {
   const FitMember& M = g.m[blockIdx.y];
@@ -765,13 +752,6 @@ bool nn_coop_enabled() {
   return on;
 }
 
-// Shells the fitness search reads before it tests the shell bound for the first time (env LSR_NN_FINE_RINGS, read once): 0 lets a
-// query whose own cell already proves its neighbour stop there.
-static int nn_fitness_fine_rings() {
-  static const int v = [] { const char* e = getenv("LSR_NN_FINE_RINGS"); const int r = e ? atoi(e) : NN_FITNESS_FINE_RINGS; return r < 0 ? 0 : r > 4 ? 4 : r; }();
-  return v;
-}
-
 int nn_search_device(const DeviceCloud& q, const float* d_T16, const HashGridDev& grid, int fine_rings, float max_d2,
                      int* d_idx, float* d_d2, hipStream_t stream, int* d_work) {
   const int n = (int)q.n;
@@ -851,7 +831,7 @@ int nn_fitness_begin(const DeviceCloud& source, const float* T16_host, const Has
   if (st) return st;
   LSR_HIP(hipMemcpyAsync(d_T16.p, T16_host, 16 * sizeof(float), hipMemcpyHostToDevice, stream));
   const float max_d2 = (max_range >= 3.0e38) ? INFINITY : (float)max_range * 1.0001f;
-  if ((st = nn_search_device(source, d_T16.p, grid, nn_fitness_fine_rings(), max_d2, d_idx, d_d2, stream, d_work))) return st;
+  if ((st = nn_search_device(source, d_T16.p, grid, NN_FITNESS_FINE_RINGS, max_d2, d_idx, d_d2, stream, d_work))) return st;
   const int nb = 256;
   hipLaunchKernelGGL(fitness_partial_kernel, dim3(nb), dim3(256), 0, stream, d_idx, d_d2, (int)source.n, max_range, d_part);
   if ((st = sc.ensure_mailbox())) return st;
@@ -872,7 +852,7 @@ int nn_fitness_begin_group(const FitJob* jobs, int count, hipStream_t stream) {
     FitGroup grp;
     std::memset(&grp, 0, sizeof(grp));
     const int ng = std::min(FIT_GROUP, count - g0);
-    int max_blocks = 1, max_n = 0;
+    int max_n = 0;
     for (int k = 0; k < ng; k++) {
       const FitJob& J = jobs[g0 + k];
       BuildScratch& sc = *J.sc;
@@ -887,36 +867,22 @@ int nn_fitness_begin_group(const FitJob* jobs, int count, hipStream_t stream) {
       M.G = make_view(*J.grid);
       M.qx = J.source->x(); M.qy = J.source->y(); M.qz = J.source->z();
       M.n = (int)J.source->n;
-      M.blocks = (int)(((long)M.n * 64 + 255) / 256);
       M.empty = (J.grid->n_blocks == 0 || M.n == 0) ? 1 : 0;   // no finite target point: no pair, the score is DBL_MAX (nn_fitness_end)
       for (int a = 0; a < 16; a++) M.T16[a] = J.T16[a];
       M.max_d2 = (J.max_range >= 3.0e38) ? INFINITY : (float)J.max_range * 1.0001f;
       M.max_range = J.max_range;
       M.idx = d_idx; M.d2 = d_d2; M.part = d_part; M.work = d_work;
       M.mb = sc.d_mb; M.token = token;
-      M.fine_rings = nn_fitness_fine_rings();
-      static const int ball_cells = [] { const char* e = getenv("LSR_FIT_BALL_CELLS"); const int v = e ? atoi(e) : FIT_BALL_CELLS; return v < 1 ? 1 : v > 8 ? 8 : v; }();
-      M.ball_cells = ball_cells;
-      if (!M.empty) { max_blocks = std::max(max_blocks, M.blocks); max_n = std::max(max_n, M.n); }
+      if (!M.empty) max_n = std::max(max_n, M.n);
     }
-    static const int form = [] { const char* e = getenv("LSR_FIT_GROUP_FORM"); return e ? atoi(e) : -1; }();   // 0 wave, 1 quad + tail, -1 by size
-    const bool quad_form = form == 1;   // measured on 64 candidates x 30k queries: 5.85 ms against 3.54 ms for one wave per query
-    const bool ball_form = form == 2 || form < 0;   // sixteen lanes per query seeded by its own fine cell + a tail for the rest (default)
-    if (ball_form) {
-      hipLaunchKernelGGL(fit_zero_work_group_kernel, dim3(1), dim3(ng), 0, stream, grp);
-      hipLaunchKernelGGL(nn1_ball_group_kernel, dim3((unsigned)(((long)max_n * 16 + 255) / 256), ng), dim3(256), 0, stream, grp);
-      // the rest (one wave per query, a stride loop over the member's work list): a member whose scan leaves the submap puts
-      // thousands of queries there, each a walk of 10-30 us; a small group gives such a member more waves (round 5: a share of 8
-      // with one such member spent 114 us here on 1 024 waves per member; the answers do not depend on the geometry)
-      const unsigned list_wgs = ng <= 8 ? 1024u : 256u;
-      hipLaunchKernelGGL(nn1_list_group_kernel, dim3(list_wgs, ng), dim3(256), 0, stream, grp);
-    } else if (quad_form) {
-      hipLaunchKernelGGL(fit_zero_work_group_kernel, dim3(1), dim3(ng), 0, stream, grp);
-      hipLaunchKernelGGL(nn1_quad_group_kernel, dim3((unsigned)(((long)max_n * 4 + NN_THREADS - 1) / NN_THREADS), ng), dim3(NN_THREADS), 0, stream, grp);
-      hipLaunchKernelGGL(nn1_coop_group_kernel, dim3(64, ng), dim3(256), 0, stream, grp);
-    } else {
-      hipLaunchKernelGGL(nn1_wave_group_kernel, dim3(max_blocks, ng), dim3(256), 0, stream, grp);
-    }
+    // sixteen lanes per query seeded by its own fine cell ...
+    hipLaunchKernelGGL(fit_zero_work_group_kernel, dim3(1), dim3(ng), 0, stream, grp);
+    hipLaunchKernelGGL(nn1_ball_group_kernel, dim3((unsigned)(((long)max_n * 16 + 255) / 256), ng), dim3(256), 0, stream, grp);
+    // ... and the rest (one wave per query, a stride loop over the member's work list): a member whose scan leaves the submap puts
+    // thousands of queries there, each a walk of 10-30 us; a small group gives such a member more waves (round 5: a share of 8
+    // with one such member spent 114 us here on 1 024 waves per member; the answers do not depend on the geometry)
+    const unsigned list_wgs = ng <= 8 ? 1024u : 256u;
+    hipLaunchKernelGGL(nn1_list_group_kernel, dim3(list_wgs, ng), dim3(256), 0, stream, grp);
     hipLaunchKernelGGL(fitness_partial_group_kernel, dim3(256, ng), dim3(256), 0, stream, grp);
     hipLaunchKernelGGL(fitness_final_group_kernel, dim3(ng), dim3(256), 0, stream, grp);
   }

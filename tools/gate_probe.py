@@ -17,6 +17,5 @@ torch.cuda.synchronize()
 ts = []
 for _ in range(40):
     t0 = time.perf_counter(); edges = search_loop(back, sms, LoopClosureParams(**lp)); ts.append(time.perf_counter() - t0)
-print("loop gate: median %.3f ms p10 %.3f p90 %.3f | fitness %.6f accepted %s | env NN_FROM_GRID=%s" % (
-    1e3 * np.median(ts), 1e3 * np.percentile(ts, 10), 1e3 * np.percentile(ts, 90), edges[0].fitness_score, edges[0].accepted,
-    os.environ.get("LSR_NN_FROM_GRID", "1")), flush=True)
+print("loop gate: median %.3f ms p10 %.3f p90 %.3f | fitness %.6f accepted %s" % (
+    1e3 * np.median(ts), 1e3 * np.percentile(ts, 10), 1e3 * np.percentile(ts, 90), edges[0].fitness_score, edges[0].accepted), flush=True)
