@@ -82,9 +82,7 @@ typedef enum lsr_key {
                                          the rounds 1-3 kernel) is accepted and means automatic; as an environment preset an
                                          unknown value is reported on stderr and ignored */
   LSR_NDT_TABLE_MODE = 41,            /* where the pass reads leaf records: -1 = automatic, 0 = dense global table,
-                                         1 = compact global table, 2 = whole table staged in LDS (when it fits), 3 = per
-                                         workgroup the box of cells its tile-ordered points touch staged in LDS (dense tables
-                                         that do not fit LDS: ndt_resolution <= 2 m on a 20-frame submap) */
+                                         1 = compact global table, 2 = whole table staged in LDS (when it fits) */
   LSR_GRID_BUILDER = 42,              /* 0 = automatic (counting sort for <= 16383 grid cells, radix sort beyond), 1 = always
                                          the radix-sort builder */
   LSR_WAIT_MODE = 43,                 /* how the calling thread waits for the device inside align() / setInputTarget():
@@ -95,9 +93,7 @@ typedef enum lsr_key {
   LSR_NDT_QUAD = 44,                  /* single NDT registrations: 1 = quad kernel (four lanes per source point on every CU:
                                          lowest latency for a 30k-point scan), 0 = lane kernel (one lane per point: what candidate
                                          sets use), -1 = automatic (quad below 65 536 source points, lane from there on) */
-  LSR_NDT_SORT = 45,                  /* order the source by voxel tile of its guess-moved points at the start of align():
-                                         -1 = automatic (tile table mode only), 0 = never (the tile mode then falls back to the
-                                         global table), 1 = also when the records are gathered from the global table */
+  /* 45 is unassigned (formerly LSR_NDT_SORT): the other keys keep their numbers */
   LSR_VOXEL_FILTER_FORM = 46,         /* read-only (lsr_get_i32): which form the last VoxelGrid filter on this object took:
                                          0 = none yet, 1 = grid dimensions worked out on the host (one wait for the bounding box,
                                          one for the leaf count), 2 = on the device (one wait: from the second

@@ -137,7 +137,6 @@ int device_cus(int device) {
 // chip holds at once — two 512-thread workgroups of the quad kernel (128 points each) or of the lane kernel per CU, one of its
 // 1024-thread workgroups — and lets each of them walk several batches of points instead.
 // `threads`: THREADS per workgroup; `points`: source points a workgroup takes per trip (quad kernel: threads / 4).
-constexpr int NDT_QUAD_BATCH_MAX = 1;
 constexpr int NDT_LANE_SINGLE_MIN = 65536;   // source points from which a single registration uses the lane kernel
 int ndt_resident_wgs(int device, int threads) {
   // two 512-thread workgroups per CU (128 VGPRs per lane: four waves per SIMD; the lane kernel's LDS table + staging tiles fit twice),
@@ -173,13 +172,12 @@ int device_lds_bytes(int device) {
   if (device >= 0 && device < 64) cached[device] = v;
   return v;
 }
-constexpr int NDT_QUAD_STATIC_LDS = 32 * 1024;   // static LDS of the quad kernel next to its table / tile buffer (27 KiB + margin)
+constexpr int NDT_QUAD_STATIC_LDS = 32 * 1024;   // static LDS of the quad kernel next to its table (27 KiB + margin)
 constexpr int NDT_LANE_STATIC_LDS = 6 * 1024;    // ... of the lane kernel (bins, state image; its staging tiles are dynamic LDS)
 
 void fill_problem(NdtProblem& P, lsr_handle h, NdtState* d_state, long long* d_bins, const NdtLaunchCfg& cfg) {
   const VoxelGridDev& g = h->target->grid;
-  const DeviceCloud& src = cfg.sorted ? h->source_sorted : h->source;   // the tile-ordered copy (always in tile mode)
-  P.sx = src.x(); P.sy = src.y(); P.sz = src.z();
+  P.sx = h->source.x(); P.sy = h->source.y(); P.sz = h->source.z();
   P.n = (int)h->source.n;
   P.nblocks = ndt_nblocks(h->source.n, h->device, cfg.batch, cfg_wg_threads(cfg), cfg_wg_points(cfg));
   P.lds_image = g.lds_image.p;
@@ -191,7 +189,6 @@ void fill_problem(NdtProblem& P, lsr_handle h, NdtState* d_state, long long* d_b
   P.mul1 = g.div_b[0];
   P.mul2 = g.div_b[0] * g.div_b[1];
   P.leaf = g.leaf;
-  P.tile_bytes = (cfg.tab == NDT_TAB_TILE) ? cfg.lds_bytes : 0;
   P.st = d_state;
   P.bins = d_bins;
   P.mailbox = nullptr;
@@ -203,8 +200,7 @@ void fill_problem(NdtProblem& P, lsr_handle h, NdtState* d_state, long long* d_b
 
 // Where the derivative pass reads the leaf records, and with which kernel.  grids: the batch's targets.
 //  every table fits LDS            -> NDT_TAB_LDS   (quad kernel for one registration, one-lane kernel for a batch)
-//  dense tables that do not fit    -> NDT_TAB_DENSE (global gathers; L2 resident at the reference's resolutions), or on request
-//                                     NDT_TAB_TILE  (quad kernel, also for batches; source ordered by voxel tile per align)
+//  dense tables that do not fit    -> NDT_TAB_DENSE (global gathers; L2 resident at the reference's resolutions)
 //  tables beyond 4 Mi cells        -> NDT_TAB_COMPACT (global gathers through cell_slot)
 // table_mode: the lead object's LSR_NDT_TABLE_MODE override (-1 automatic).
 void choose_table_mode(lsr_handle lead, lsr_handle* hs, int B, NdtLaunchCfg& cfg) {
@@ -225,7 +221,7 @@ void choose_table_mode(lsr_handle lead, lsr_handle* hs, int B, NdtLaunchCfg& cfg
   // dense global table) 9.4 us per pass with 512-thread workgroups against 16.1 us through the quad kernel (round 4)
   size_t n_max = 0;
   for (int b = 0; b < B; b++) n_max = std::max(n_max, hs[b]->source.n);
-  const bool want_quad_single = (B <= NDT_QUAD_BATCH_MAX && (lead->ndt_quad == 1 || (lead->ndt_quad < 0 && n_max < (size_t)NDT_LANE_SINGLE_MIN)));
+  const bool want_quad_single = (B == 1 && (lead->ndt_quad == 1 || (lead->ndt_quad < 0 && n_max < (size_t)NDT_LANE_SINGLE_MIN)));
   // 512 threads per workgroup (1024 on request).  A workgroup's waves share ONE compute unit: 1024 threads are four waves per SIMD
   // whatever the size of the set, 512 are two and twice the workgroups — cfg-4 sets of 4 / 8 / 16 / 64 members, align stage:
   // 0.48 / 0.50 / 0.71 / 1.98 ms with 1024 threads, 0.40 / 0.48 / 0.65 / 1.74 ms with 512 (two chains from 6 members on).
@@ -234,41 +230,33 @@ void choose_table_mode(lsr_handle lead, lsr_handle* hs, int B, NdtLaunchCfg& cfg
   const int static_lds = want_quad_single ? NDT_QUAD_STATIC_LDS : NDT_LANE_STATIC_LDS + ndt_lane_tile_bytes(lane_threads);
   const int table_cap = std::min(want_quad_single ? NDT_LDS_TABLE_MAX_QUAD : NDT_LDS_TABLE_MAX, lds_cap - static_lds);
   const bool lds_ok = all_lds && lds_max <= table_cap;
-  const bool tile_ok = all_dense && lead->ndt_quad != 0 && lead->ndt_sort != 0 && NDT_TILE_BYTES + NDT_QUAD_STATIC_LDS <= lds_cap &&
-                       lead->ndt.neighborhood != LSR_KDTREE;   // (the tile mode numbers cells per tile: no centroid lookup there)
   int tab;
   if (override_mode == NDT_TAB_COMPACT) tab = NDT_TAB_COMPACT;
   else if (override_mode == NDT_TAB_DENSE && all_dense) tab = NDT_TAB_DENSE;
-  else if (override_mode == NDT_TAB_TILE && tile_ok) tab = NDT_TAB_TILE;
   else if (override_mode == NDT_TAB_LDS && lds_ok) tab = NDT_TAB_LDS;
   else if (lds_ok) tab = NDT_TAB_LDS;
-  else tab = all_dense ? NDT_TAB_DENSE : NDT_TAB_COMPACT;   // measured: the pass is not gather bound, the tile mode's
-                                                            // extra barriers cost more than its LDS gathers save — on request only
+  else tab = all_dense ? NDT_TAB_DENSE : NDT_TAB_COMPACT;   // measured: the pass is not gather bound
   cfg.tab = tab;
   if (std::getenv("LSR_DEBUG_TABLE")) {
     static int shown = 0;
     if (shown++ < 4) fprintf(stderr, "[lidarslam_reg] table mode %d for %d member(s): LDS image up to %d bytes (cap %d, static %d)\n", tab, B, lds_max, table_cap, static_lds);
   }
-  cfg.quad = (want_quad_single || tab == NDT_TAB_TILE) ? 1 : 0;
-  cfg.lds_bytes = (tab == NDT_TAB_LDS) ? lds_max : (tab == NDT_TAB_TILE ? NDT_TILE_BYTES : 0);
+  cfg.quad = want_quad_single ? 1 : 0;
+  cfg.lds_bytes = (tab == NDT_TAB_LDS) ? lds_max : 0;
   if (cfg.quad) cfg.threads = (lead->ndt_threads == 64 || lead->ndt_threads == 128) ? lead->ndt_threads : NDT_QUAD_POINTS;  // POINTS per workgroup
   else cfg.threads = lane_threads;
   // two waves per chunk (ndt.hip: SPLIT) for a single scan whose points, one lane each, leave the chip half empty but whose chunk
   // pairs still fit it at once: 65 536 .. resident workgroups x 256 points (cfg 5: 120 000 points = 469 workgroups of 512 threads).
-  // LSR_NDT_SPLIT = 0 / 1 (key or environment preset) forces it off / on (on: any single registration that takes the 512-thread lane kernel).
+  // LSR_NDT_SPLIT = 0 / 1 (key or environment preset) forces it off / on (on: any single registration that takes the 512-thread lane
+  // kernel with a DIRECT neighbourhood: the KDTREE kernels have no split form).
   cfg.split = 0;
-  if (!cfg.quad && B == 1 && cfg.threads == 512) {
-    const size_t fits = (size_t)ndt_resident_wgs(lead->device, 512) * 256;
+  if (!cfg.quad && B == 1 && cfg.threads == 512 && lead->ndt.neighborhood != LSR_KDTREE) {
     // measured (cfg 5, 120 000 points, res 2.0 / 1.0): 9.25 / 9.33 us per pass split against 9.14 / 9.08 us with one wave per chunk —
     // the pass is bound by its fixed chain (boundary, head read, controller: ~5.5 us), not by the point loop the split halves; the
     // barrier and the second copy of the gathers eat what the shorter per-wave chain gives.  Automatic = off; kept as an A/B form
     // (same bits: tests/test_ndt_gpu.py) with its counters in profiles/r06_pmc_cfg5.md.
-    (void)fits;
     cfg.split = lead->ndt_split >= 0 ? lead->ndt_split : 0;
   }
-  // source ordered by voxel tile: always for the tile mode (its boxes are small only then); for global-table gathers on request
-  // (LSR_NDT_SORT = 1): neighbouring lanes then read neighbouring records
-  cfg.sorted = (tab == NDT_TAB_TILE) || (lead->ndt_sort == 1 && tab != NDT_TAB_LDS);
 }
 
 // A fresh target object — or the handle's current one recycled when nobody else holds it (lsr_share_target): its device
@@ -619,12 +607,6 @@ int align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* finals, 
     lsr_handle h = hs[b];
     ndt_fill_initial_state(lead->h_state.p[2 * b], guesses ? guesses + 16 * b : nullptr, h->ndt, (int)h->source.n);
     lead->h_state.p[2 * b + 1] = lead->h_state.p[2 * b];
-    if (cfg.sorted) {
-      // order this member's source by voxel tile of its guess-moved points (4 launches on its chain's stream)
-      int c = 0;
-      while (c + 1 < n_chains && b >= chain_first[c + 1]) c++;
-      if ((st = ndt_sort_source(h->source, lead->h_state.p[2 * b].T, h->target->grid, h->source_sorted, h->scratch, chain_streams[c]))) return st;
-    }
     fill_problem(lead->h_prob.p[b], h, lead->d_state.p + 2 * b, lead->d_bins.p + (size_t)b * NDT_NBANKS * NDT_BANK_WORDS, cfg);
     max_blocks = std::max(max_blocks, lead->h_prob.p[b].nblocks);
     nb_full = std::max(nb_full, (int)((h->source.n + cfg_wg_points(cfg) - 1) / cfg_wg_points(cfg)));
@@ -848,9 +830,8 @@ int lsr_create(int method, int device_id, void* stream, lsr_handle* out) {
     if (v == 64 || v == 128 || v == 512 || v == 1024) h->ndt_threads = v;
     else if (v != 0) fprintf(stderr, "[lidarslam_reg] LSR_NDT_WORKGROUP=%d ignored: 64 / 128 (quad kernel, points) or 512 / 1024 (lane kernel, threads)\n", v);
   }
-  if (const char* e = std::getenv("LSR_NDT_TABLE_MODE")) { const int v = std::atoi(e); if (v >= -1 && v <= 3) h->ndt_table_mode = v; }
+  if (const char* e = std::getenv("LSR_NDT_TABLE_MODE")) { const int v = std::atoi(e); if (v >= -1 && v <= 2) h->ndt_table_mode = v; }
   if (const char* e = std::getenv("LSR_NDT_QUAD")) { const int v = std::atoi(e); if (v >= -1 && v <= 1) h->ndt_quad = v; }
-  if (const char* e = std::getenv("LSR_NDT_SORT")) { const int v = std::atoi(e); if (v >= -1 && v <= 1) h->ndt_sort = v; }
   if (const char* e = std::getenv("LSR_NDT_SPLIT")) { const int v = std::atoi(e); if (v >= -1 && v <= 1) h->ndt_split = v; }
   if (const char* e = std::getenv("LSR_WAIT_MODE")) {   // 0 | 1 | 2 or spin | yield | sleep
     const std::string w(e);
@@ -966,14 +947,11 @@ int lsr_set_i32(lsr_handle h, int key, int v) {
       if (v != 0 && v != 64 && v != 128 && v != 512 && v != 1024) { set_last_error("NDT workgroup key must be 0 (auto), 64 / 128 (quad kernel: points) or 512 / 1024 (lane kernel: threads)"); return LSR_ERR_INVALID_ARGUMENT; }
       h->ndt_threads = v; return LSR_OK;
     case LSR_NDT_TABLE_MODE:
-      if (v < -1 || v > 3) { set_last_error("NDT table mode must be -1 (auto), 0 dense, 1 compact, 2 LDS, 3 tile"); return LSR_ERR_INVALID_ARGUMENT; }
+      if (v < -1 || v > 2) { set_last_error("NDT table mode must be in -1 .. 2: -1 (auto), 0 dense, 1 compact, 2 LDS"); return LSR_ERR_INVALID_ARGUMENT; }
       h->ndt_table_mode = v; return LSR_OK;
     case LSR_NDT_QUAD:
       if (v < -1 || v > 1) { set_last_error("NDT quad mode must be -1 (auto), 0 or 1"); return LSR_ERR_INVALID_ARGUMENT; }
       h->ndt_quad = v; return LSR_OK;
-    case LSR_NDT_SORT:
-      if (v < -1 || v > 1) { set_last_error("NDT source ordering must be -1 (auto), 0 or 1"); return LSR_ERR_INVALID_ARGUMENT; }
-      h->ndt_sort = v; return LSR_OK;
     case LSR_NDT_SPLIT:
       if (v < -1 || v > 1) { set_last_error("NDT split mode must be -1 (auto), 0 or 1"); return LSR_ERR_INVALID_ARGUMENT; }
       h->ndt_split = v; return LSR_OK;
@@ -1004,7 +982,6 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_NDT_WORKGROUP: *v = h->ndt_threads; return LSR_OK;
     case LSR_NDT_TABLE_MODE: *v = h->ndt_table_mode; return LSR_OK;
     case LSR_NDT_QUAD: *v = h->ndt_quad; return LSR_OK;
-    case LSR_NDT_SORT: *v = h->ndt_sort; return LSR_OK;
     case LSR_NDT_SPLIT: *v = h->ndt_split; return LSR_OK;
     case LSR_GRID_BUILDER: *v = h->scratch.force_sort_path ? 1 : 0; return LSR_OK;
     case LSR_WAIT_MODE: *v = h->scratch.wait_mode; return LSR_OK;
@@ -1695,7 +1672,7 @@ int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, si
     for (int e = 0; e < k_eval; e++) {
       lsr_handle a = h->aux[e].get();
       a->ndt = h->ndt; a->gicp = h->gicp;
-      a->ndt_threads = h->ndt_threads; a->ndt_table_mode = h->ndt_table_mode; a->ndt_quad = h->ndt_quad; a->ndt_sort = h->ndt_sort;
+      a->ndt_threads = h->ndt_threads; a->ndt_table_mode = h->ndt_table_mode; a->ndt_quad = h->ndt_quad;
       a->scratch.wait_mode = h->scratch.wait_mode; a->scratch.force_sort_path = h->scratch.force_sort_path;
       int st = a->source.resize(h->source.n);
       if (st) return st;
@@ -1927,7 +1904,6 @@ int lsr_ndt_derivatives(lsr_handle h, const double* p6, const float* T16, int co
   cfg.max_blocks = ndt_nblocks(h->source.n, h->device, 1, cfg_wg_threads(cfg), cfg_wg_points(cfg));
   ndt_fill_diag_state(h->h_state.p[0], p6, T16, compute_hessian, h->ndt, (int)h->source.n);
   h->h_state.p[1] = h->h_state.p[0];
-  if (cfg.sorted && (st = ndt_sort_source(h->source, h->h_state.p[0].T, h->target->grid, h->source_sorted, h->scratch, h->stream))) return st;
   fill_problem(h->h_prob.p[0], h, h->d_state.p, h->d_bins.p, cfg);
   LSR_HIP(hipMemcpyAsync(h->d_prob.p, h->h_prob.p, sizeof(NdtProblem), hipMemcpyHostToDevice, h->stream));
   LSR_HIP(hipMemcpyAsync(h->d_state.p, h->h_state.p, 2 * sizeof(NdtState), hipMemcpyHostToDevice, h->stream));

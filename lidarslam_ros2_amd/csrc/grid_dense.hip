@@ -162,14 +162,10 @@ __device__ __forceinline__ void vg_scan_kernel_body(const unsigned short* __rest
     if (seg == VG_SCAN_SEGS - 1) total[k] = run;
   }
 }
-__global__ __launch_bounds__(256) void vg_scan_kernel(const unsigned short* __restrict__ hist, int nblk, int C,
-                                                      unsigned int* __restrict__ blkoff, unsigned int* __restrict__ total) {
-  vg_scan_kernel_body(hist, nblk, C, blkoff, total, (int)blockIdx.x);
-}
 
 // one workgroup: exclusive scan over the cells -> start[0..C] (start[C] = n)
 __device__ __forceinline__ void vg_cellscan_kernel_body(const unsigned int* __restrict__ total, int C, unsigned int* __restrict__ start,
-                                                        unsigned int* __restrict__ rank /*nullable*/, const int blk_x) {
+                                                        unsigned int* __restrict__ rank) {
   // counts and occupancy flags of a thread's slice, a scan inside every wave (shuffles), one barrier, the waves' totals added up by
   // every thread (until round 5: a Hillis-Steele scan over 1024 LDS words, twenty barriers of sixteen waves each: 6.2 -> 4.7 us)
   __shared__ unsigned int s_ws[16], s_wo[16];
@@ -191,13 +187,9 @@ __device__ __forceinline__ void vg_cellscan_kernel_body(const unsigned int* __re
   for (int c = c0; c < c1; c++) {
     const unsigned int t = total[c];
     start[c] = run; run += t;
-    if (rank) { rank[c] = rrun; rrun += (t != 0u); }   // rank of the cell among the cells that hold points (the sentinel bin counts too: it is last)
+    rank[c] = rrun; rrun += (t != 0u);   // rank of the cell among the cells that hold points (the sentinel bin counts too: it is last)
   }
   if (tid == 1023) start[C] = all;
-}
-__global__ __launch_bounds__(1024) void vg_cellscan_kernel(const unsigned int* __restrict__ total, int C, unsigned int* __restrict__ start,
-                                                           unsigned int* __restrict__ rank) {
-  vg_cellscan_kernel_body(total, C, start, rank, (int)blockIdx.x);
 }
 
 // Scatter into cell order.  Wave w of block b owns points [b*4096 + w*1024, +1024) and walks them in 16 steps of
@@ -207,7 +199,7 @@ __global__ __launch_bounds__(1024) void vg_cellscan_kernel(const unsigned int* _
 __device__ __forceinline__ void vg_scatter_kernel_body(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
                                                          int n, const unsigned short* __restrict__ keys, const unsigned int* __restrict__ blkoff,
                                                          const unsigned int* __restrict__ start, int C, float* __restrict__ ox,
-                                                         float* __restrict__ oy, float* __restrict__ oz, int* __restrict__ oidx /*nullable*/,
+                                                         float* __restrict__ oy, float* __restrict__ oz, int* __restrict__ oidx,
                                                          const int blk_x) {
   extern __shared__ unsigned long long s_c[];  // [C]
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -250,15 +242,9 @@ __device__ __forceinline__ void vg_scatter_kernel_body(const float* __restrict__
       const unsigned long long old = atomicAdd(&s_c[k], 1ull << sh);
       const unsigned int pos = absb[j] + ((unsigned int)(old >> sh) & 0xFFFFu);
       ox[pos] = px[j]; oy[pos] = py[j]; oz[pos] = pz[j];
-      if (oidx) oidx[pos] = base_i + j * 64;
+      oidx[pos] = base_i + j * 64;
     }
   }
-}
-__global__ __launch_bounds__(256) void vg_scatter_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                                                         int n, const unsigned short* __restrict__ keys, const unsigned int* __restrict__ blkoff,
-                                                         const unsigned int* __restrict__ start, int C, float* __restrict__ ox,
-                                                         float* __restrict__ oy, float* __restrict__ oz, int* __restrict__ oidx) {
-  vg_scatter_kernel_body(x, y, z, n, keys, blkoff, start, C, ox, oy, oz, oidx, (int)blockIdx.x);
 }
 
 // K1 + K2, one WAVE per grid cell: lane l sums the cell's points l + 64*t (cell order = point order), the lanes are combined by a
@@ -450,7 +436,7 @@ __global__ __launch_bounds__(256) void vg_scan_group_kernel(const VgGroup g) {
 }
 __global__ __launch_bounds__(1024) void vg_cellscan_group_kernel(const VgGroup g) {
   const VgMember& M = g.m[blockIdx.x];
-  vg_cellscan_kernel_body(M.total, M.ncells + 1, M.start, M.rank, 0);
+  vg_cellscan_kernel_body(M.total, M.ncells + 1, M.start, M.rank);
 }
 __global__ __launch_bounds__(256) void vg_scatter_group_kernel(const VgGroup g) {
   const VgMember& M = g.m[blockIdx.y];
@@ -472,79 +458,7 @@ __global__ __launch_bounds__(256) void vg_leaf_finish_group_kernel(const VgGroup
   vg_leaf_finish_body(M.start, M.ncells, 6, 0.01, M.rec, M.mean64, M.icov64, M.leaf_key, M.leaf_n, M.cell_slot, (int)(blockIdx.x * 256 + threadIdx.x));
 }
 
-// ---- source ordering for the tile-staged derivative pass (NDT_TAB_TILE) -------------------------------------------------
-// key of a source point = Morton code of the (2^shift x 2^shift cells) x (all z) column of the target grid its image under
-// the initial guess falls into, clamped to the grid; non-finite points get the sentinel key (sorted last).  The counting
-// sort itself is the grid builder's (vg_scan / vg_cellscan / vg_scatter): stable, deterministic, no host round trip.
-struct SrcSortT { float t[12]; };
-__device__ __forceinline__ unsigned int spread7(unsigned int v) {   // bit i of v -> bit 2 i
-  v = (v | (v << 4)) & 0x0F0Fu;
-  v = (v | (v << 2)) & 0x3333u;
-  v = (v | (v << 1)) & 0x5555u;
-  return v;
-}
-__global__ __launch_bounds__(256) void src_hist_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                                                       int n, const SrcSortT T, float leaf, int mb0, int mb1, int d0, int d1, int shift, int nkeys,
-                                                       unsigned short* __restrict__ keys, unsigned short* __restrict__ hist) {
-  extern __shared__ unsigned int s_hist[];  // [nkeys + 1]
-  const int C = nkeys + 1, tid = threadIdx.x;
-  for (int k = tid; k < C; k += 256) s_hist[k] = 0u;
-  __syncthreads();
-  const int base = blockIdx.x * VG_CHUNK;
-#pragma unroll 4
-  for (int j = 0; j < VG_CHUNK / 256; j++) {
-    const int i = base + j * 256 + tid;
-    if (i < n) {
-      const float px = x[i], py = y[i], pz = z[i];
-      unsigned int k = (unsigned int)nkeys;
-      if (isfinite(px) && isfinite(py) && isfinite(pz)) {
-        const float tx = fmaf(T.t[0], px, fmaf(T.t[1], py, fmaf(T.t[2], pz, T.t[3])));
-        const float ty = fmaf(T.t[4], px, fmaf(T.t[5], py, fmaf(T.t[6], pz, T.t[7])));
-        const float fx = fminf(fmaxf(floorf(tx / leaf) - (float)mb0, 0.f), (float)(d0 - 1));   // NaN / inf images clamp too
-        const float fy = fminf(fmaxf(floorf(ty / leaf) - (float)mb1, 0.f), (float)(d1 - 1));
-        const unsigned int cx = (unsigned int)(int)fx >> shift, cy = (unsigned int)(int)fy >> shift;
-        k = spread7(cx) | (spread7(cy) << 1);
-        if (k >= (unsigned int)nkeys) k = (unsigned int)nkeys - 1u;
-      }
-      keys[i] = (unsigned short)k;
-      atomicAdd(&s_hist[k], 1u);
-    }
-  }
-  __syncthreads();
-  unsigned short* row = hist + (size_t)blockIdx.x * C;
-  for (int k = tid; k < C; k += 256) row[k] = (unsigned short)s_hist[k];
-}
-
 }  // namespace
-
-int ndt_sort_source(const DeviceCloud& src, const float* T12, const VoxelGridDev& grid, DeviceCloud& out, BuildScratch& sc, hipStream_t stream) {
-  const int n = (int)src.n;
-  int st = out.resize(src.n);
-  if (st) return st;
-  if (n == 0) return LSR_OK;
-  // columns of 2^shift x 2^shift cells, at most 64 x 64 of them: Morton keys below 4096
-  int shift = 0;
-  while (((grid.div_b[0] + (1 << shift) - 1) >> shift) > 64 || ((grid.div_b[1] + (1 << shift) - 1) >> shift) > 64) shift++;
-  const int nkeys = 4096, C = nkeys + 1;
-  const int nblk = (n + VG_CHUNK - 1) / VG_CHUNK;
-  const size_t w_total = (size_t)C, w_start = (size_t)C + 1, w_blkoff = (size_t)nblk * C, w_hist = ((size_t)nblk * C + 1) / 2, w_keys = ((size_t)n + 1) / 2;
-  if ((st = sc.words.reserve(16 + w_total + w_start + w_blkoff + w_hist + w_keys + 16))) return st;
-  unsigned int* total = sc.words.p + 16;
-  unsigned int* start = total + w_total;
-  unsigned int* blkoff = start + w_start;
-  unsigned short* hist = reinterpret_cast<unsigned short*>(blkoff + w_blkoff);
-  unsigned short* keys = reinterpret_cast<unsigned short*>(blkoff + w_blkoff + w_hist);
-  SrcSortT T;
-  for (int k = 0; k < 12; k++) T.t[k] = T12[k];
-  hipLaunchKernelGGL(src_hist_kernel, dim3(nblk), dim3(256), (size_t)C * 4, stream, src.x(), src.y(), src.z(), n, T, grid.leaf, grid.min_b[0],
-                     grid.min_b[1], grid.div_b[0], grid.div_b[1], shift, nkeys, keys, hist);
-  hipLaunchKernelGGL(vg_scan_kernel, dim3((C + 31) / 32), dim3(256), 0, stream, hist, nblk, C, blkoff, total);
-  hipLaunchKernelGGL(vg_cellscan_kernel, dim3(1), dim3(1024), 0, stream, total, C, start, (unsigned int*)nullptr);
-  hipLaunchKernelGGL(vg_scatter_kernel, dim3(nblk), dim3(256), (size_t)C * 8, stream, src.x(), src.y(), src.z(), n, keys, blkoff, start, C,
-                     out.x(), out.y(), out.z(), (int*)nullptr);
-  LSR_HIP(hipGetLastError());
-  return LSR_OK;
-}
 
 // ---- host side of the group kernels -----------------------------------------------------------------------------------
 int ndt_targets_ingest(TargetBuildJob* jobs, int count, hipStream_t stream) {

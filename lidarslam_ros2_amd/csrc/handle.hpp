@@ -50,12 +50,10 @@ struct lsr_handle_s {
   int ndt_table_mode = -1;   // LSR_NDT_TABLE_MODE: -1 = automatic, else lsr::NdtTableMode
   int ndt_quad = -1;         // LSR_NDT_QUAD: -1 = automatic (single registrations: four lanes per point), 0 = lane kernel, 1 = four
   int ndt_split = -1;        // LSR_NDT_SPLIT: -1 = automatic, 0 / 1 = one / two waves per chunk in the 512-thread lane kernel (single registrations)
-  int ndt_sort = -1;         // LSR_NDT_SORT: -1 = automatic (tile mode only), 0 = never, 1 = also for global-table gathers
 
   std::shared_ptr<TargetData> target;
   std::shared_ptr<TargetData> spare_target;  // recycled by the next setInputTarget when no other handle shares it
   DeviceCloud source;
-  DeviceCloud source_sorted;  // NDT_TAB_TILE: the source ordered by voxel tile of its guess-moved points (rebuilt by every align)
   DeviceCloud raw, filtered;  // N1: unfiltered upload / stand-alone filter result
   bool has_source = false;
   bool source_cov_valid = false;

@@ -18,6 +18,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "grid_device.hpp"
 #include "ndt_point.hpp"
@@ -853,8 +854,8 @@ __device__ __forceinline__ void add_piece_lds(unsigned long long* ibin, const in
 // buffered by launch parity (launch seq reads state[seq & 1]; workgroup 0 writes state[(seq + 1) & 1]), the banks rotate
 // (launch seq adds to bank seq % 3, reads bank (seq - 1) % 3 and clears bank (seq + 1) % 3), so a late-starting workgroup
 // can never observe a value produced by its own launch.
-//  BYVAL: a single-registration launch carries its NdtProblem in the kernel arguments, which removes one dependent memory
-//         round trip from the latency chain of every pass.
+//  A single-registration launch carries its NdtProblem in the kernel arguments (the quad kernel always, the lane kernel in
+//         its by-value form), which removes one dependent memory round trip from the latency chain of every pass.
 //  TAB:   where the leaf records live (NdtTableMode).  NDT_TAB_LDS stages the whole valid-voxel table (uint16 cell->slot map +
 //         48-byte records) into LDS with wave-wide 16-byte global->LDS DMA issued right after the state has landed: the copy
 //         flies while wave 0 runs the controller, and the dependent gathers of a point become ds_read_b128.
@@ -879,34 +880,12 @@ __device__ __forceinline__ float dpp_quad_sum(float v) {
   return v;
 }
 
-// min / max over the lanes of a wave (every lane receives the result)
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int m = 4; m <= 32; m <<= 1) v = min(v, __shfl_xor(v, m, 64));   // the four lanes of a quad hold the same value
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int m = 4; m <= 32; m <<= 1) v = max(v, __shfl_xor(v, m, 64));
-  return v;
-}
-// n / d for small n through a precomputed magic number m = 2^32 / d + 1 (exact for n, d < 65536; d = 1 has no such m)
-__device__ __forceinline__ unsigned int div_magic(unsigned int d) { return 0xFFFFFFFFu / d + 1u; }
-__device__ __forceinline__ unsigned int div_small(unsigned int n, unsigned int d, unsigned int m) { return d == 1u ? n : __umulhi(n, m); }
-
 // TAB (NdtTableMode) of the quad kernel:
 //  NDT_TAB_LDS   the whole valid-voxel table staged into LDS at the head of the launch (tables that fit: res 5.0);
-//  NDT_TAB_TILE  per workgroup and per pass, the BOX of grid cells its points touch (bounding box of their centre cells + the
-//                one-cell halo of the neighbourhood) is gathered from the dense global table into LDS with global->LDS DMA
-//                (48 of the 64 bytes of every record, one 16-byte piece per lane), and the 7 x 3 dependent gathers of a point
-//                become ds_read_b128.  The source is ordered by voxel tile at the start of the align (ndt_sort_source), so a
-//                workgroup's 128 points are neighbours in space — and stay neighbours under any rigid motion the line search
-//                applies — and their box is a few dozen cells.  A box beyond the tile buffer (scattered points) makes that
-//                workgroup read the global table directly for that pass, as NDT_TAB_DENSE does for all.
 //  NDT_TAB_DENSE / NDT_TAB_COMPACT  records gathered from global memory.
-// BYVAL: the problem travels in the kernel arguments (single registrations); otherwise probs[blockIdx.y] (batches).
-template <int NOFF, int TAB, int PTS, bool BYVAL, bool KD = false>
-__global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem pv, const NdtProblem* __restrict__ probs, const int seq) {
+// One registration per launch; its problem travels in the kernel arguments.
+template <int NOFF, int TAB, int PTS, bool KD = false>
+__global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem P, const int seq) {
   constexpr int THREADS = 4 * PTS;
   // floats per row of the per-point buffers, chosen against the 32-lane groups of ds_*_b32: phase A writes rows
   // ql + 4m at columns pq (4 rows x 8 columns per group): pitch = 8 (mod 32) spreads them over all 32 banks; phase C reads
@@ -914,7 +893,6 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
   constexpr int PITCH_PT = PTS + 8, PITCH_O = PTS + 4;   // s_o rows 16-byte aligned, four banks apart (phase C reads runs with ds_read_b128)
   constexpr int NT = (NOFF + 3) / 4;       // neighbours per lane
   static_assert(PTS % 64 == 0, "a workgroup batch is a whole number of canonical chunks");
-  const NdtProblem& P = BYVAL ? pv : probs[blockIdx.y];
   if ((int)blockIdx.x >= P.nblocks) return;
   const int tid = threadIdx.x, ql = tid & 3, pq = tid >> 2;
   LSR_STAMP(0)
@@ -928,7 +906,6 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
   __shared__ unsigned long long s_ibin[NDT_NBINS * 32];   // workgroups that walk several batches collect their pieces here first
   __shared__ double s_sum[NDT_NRED];
   __shared__ double s_lu[8][2];
-  __shared__ int s_box[8];               // NDT_TAB_TILE: min (0..2) / max (3..5) centre cell of this workgroup's points
   constexpr int STATE_Q = (int)(sizeof(NdtState) / 16);
   __shared__ uint4 s_state_q[STATE_Q];
   unsigned int* s_state = reinterpret_cast<unsigned int*>(s_state_q);
@@ -962,7 +939,6 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
       s_ibin[tid] = 0ull;
     }
     if (tid < STATE_Q) s_state_q[tid] = stq;
-    if (TAB == NDT_TAB_TILE && tid >= THREADS - 6) s_box[THREADS - 1 - tid] = (THREADS - 1 - tid < 3) ? INT_MAX : INT_MIN;
     // issued after the shared lines have landed, on purpose (see the one-lane kernel): these fly across the head's barriers
     if (i < P.n) { x = P.sx[i]; y = P.sy[i]; z = P.sz[i]; }
     if (tid < 64) ang_entry = k_angle_entries[tid];
@@ -1059,7 +1035,6 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
 
   const unsigned short* s_map = reinterpret_cast<const unsigned short*>(s_table);
   const float4* s_rec = reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(s_table) + P.lds_map_bytes);
-  const float4* s_tile = reinterpret_cast<const float4*>(s_table);
 
   // Per batch of PTS points:
   //  A (all 4 PTS lanes, four per point): transform, neighbourhood, pair terms, quad combine;
@@ -1081,59 +1056,6 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
       const bool finite_ok = (i < P.n) && (fabsf(fx) < 1.0e9f) && (fabsf(fy) < 1.0e9f) && (fabsf(fz) < 1.0e9f);
       const int ci = finite_ok ? (int)fx : INT_MIN / 2, cj = finite_ok ? (int)fy : INT_MIN / 2, ck = finite_ok ? (int)fz : INT_MIN / 2;
 
-      // ---- NDT_TAB_TILE: the box of cells this batch touches -> LDS
-      bool use_tile = false;
-      int lo0 = 0, lo1 = 0, lo2 = 0, tdx = 1, tdxy = 1;
-      if (TAB == NDT_TAB_TILE) {
-        // centre cells that can have a neighbour inside the grid: within one cell of it
-        const bool near = (ci >= P.min_b[0] - 1) & (ci <= P.max_b[0] + 1) & (cj >= P.min_b[1] - 1) & (cj <= P.max_b[1] + 1) &
-                          (ck >= P.min_b[2] - 1) & (ck <= P.max_b[2] + 1);
-        const int mn0 = wave_min_i(near ? ci : INT_MAX), mn1 = wave_min_i(near ? cj : INT_MAX), mn2 = wave_min_i(near ? ck : INT_MAX);
-        const int mx0 = wave_max_i(near ? ci : INT_MIN), mx1 = wave_max_i(near ? cj : INT_MIN), mx2 = wave_max_i(near ? ck : INT_MIN);
-        if ((tid & 63) == 0 && mn0 != INT_MAX) {
-          atomicMin(&s_box[0], mn0); atomicMin(&s_box[1], mn1); atomicMin(&s_box[2], mn2);
-          atomicMax(&s_box[3], mx0); atomicMax(&s_box[4], mx1); atomicMax(&s_box[5], mx2);
-        }
-        barrier_lds_only();
-        const int b0 = uniform_i(s_box[0]), b1 = uniform_i(s_box[1]), b2 = uniform_i(s_box[2]);
-        const int b3 = uniform_i(s_box[3]), b4 = uniform_i(s_box[4]), b5 = uniform_i(s_box[5]);
-        if (b0 == INT_MAX) {
-          use_tile = true;   // no point of this batch is near the grid: every neighbour fails the bounds test, nothing is read
-        } else {
-          lo0 = max(b0 - 1, P.min_b[0]); lo1 = max(b1 - 1, P.min_b[1]); lo2 = max(b2 - 1, P.min_b[2]);
-          const int hi0 = min(b3 + 1, P.max_b[0]), hi1 = min(b4 + 1, P.max_b[1]), hi2 = min(b5 + 1, P.max_b[2]);
-          const int tdy = hi1 - lo1 + 1, tdz = hi2 - lo2 + 1;
-          tdx = hi0 - lo0 + 1;
-          tdxy = tdx * tdy;
-          const long long ncell = (long long)tdxy * tdz;
-          use_tile = ncell * NDT_LDS_REC_BYTES <= (long long)P.tile_bytes;
-          if (use_tile) {
-            // one 16-byte piece per lane and DMA instruction: piece q = 3 * (cell of the box) + part, LDS address 16 q
-            const unsigned int npieces = 3u * (unsigned int)ncell;
-            const unsigned int mxy = div_magic((unsigned int)tdxy), mx = div_magic((unsigned int)tdx);
-            const unsigned char* recb = reinterpret_cast<const unsigned char*>(P.rec);
-            unsigned char* dst = reinterpret_cast<unsigned char*>(s_table);
-            for (unsigned int q0 = (unsigned int)(tid & ~63); q0 < npieces; q0 += THREADS) {   // q0: wave-uniform
-              const unsigned int q = q0 + (unsigned int)(tid & 63);
-              if (q < npieces) {
-                const unsigned int cell = (q * 21846u) >> 16;          // q / 3 for q < 32768
-                const unsigned int part = q - 3u * cell;
-                const unsigned int c = div_small(cell, (unsigned int)tdxy, mxy);
-                const unsigned int rem = cell - c * (unsigned int)tdxy;
-                const unsigned int b = div_small(rem, (unsigned int)tdx, mx);
-                const unsigned int a = rem - b * (unsigned int)tdx;
-                const size_t gcell = (size_t)(lo0 - P.min_b[0] + (int)a) + (size_t)(lo1 - P.min_b[1] + (int)b) * P.mul1 +
-                                     (size_t)(lo2 - P.min_b[2] + (int)c) * P.mul2;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(recb + gcell * 64 + part * 16),
-                                                 (__attribute__((address_space(3))) void*)(dst + (size_t)q0 * 16), 16, 0, 0);
-              }
-            }
-          }
-        }
-        __syncthreads();   // the tile has landed (vmcnt(0) + barrier); s_box may be reset for the next batch
-        if (tid >= THREADS - 6) s_box[THREADS - 1 - tid] = (THREADS - 1 - tid < 3) ? INT_MAX : INT_MIN;
-      }
-
       bool valid[NT], score_only[NT];
       int cellv[NT];
 #pragma unroll
@@ -1146,8 +1068,7 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
         const bool in = (o < NOFF) & (a >= P.min_b[0]) & (a <= P.max_b[0]) & (b >= P.min_b[1]) & (b <= P.max_b[1]) &
                         (c >= P.min_b[2]) & (c <= P.max_b[2]);
         valid[t] = in;
-        if (TAB == NDT_TAB_TILE && use_tile) cellv[t] = in ? ((a - lo0) + (b - lo1) * tdx + (c - lo2) * tdxy) : 0;
-        else cellv[t] = in ? ((a - P.min_b[0]) + (b - P.min_b[1]) * P.mul1 + (c - P.min_b[2]) * P.mul2) : 0;
+        cellv[t] = in ? ((a - P.min_b[0]) + (b - P.min_b[1]) * P.mul1 + (c - P.min_b[2]) * P.mul2) : 0;
       }
       if (KD) {   // KDTREE (a template form of its own: the DIRECT26 kernels keep their registers): of the 27 cells, the leaves whose centroid
                   // the kd-tree's radius search would return
@@ -1173,13 +1094,6 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
           r0[t] = s_rec[slot[t] * 3 + 0];
           r1[t] = s_rec[slot[t] * 3 + 1];
           r2[t] = s_rec[slot[t] * 3 + 2];
-        }
-      } else if (TAB == NDT_TAB_TILE && use_tile) {
-#pragma unroll
-        for (int t = 0; t < NT; t++) {   // unusable cells of the box hold NaN records: the pair drops itself
-          r0[t] = s_tile[cellv[t] * 3 + 0];
-          r1[t] = s_tile[cellv[t] * 3 + 1];
-          r2[t] = s_tile[cellv[t] * 3 + 2];
         }
       } else {
         size_t ridx[NT];
@@ -1310,9 +1224,9 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
         }
       }
     }
-    // the next batch writes s_pt / s_o again: with Hessian (and in tile mode) its writes are behind a barrier of the next round;
-    // a gradient-only round without the tile barriers writes s_o straight away
-    if (!hess && TAB != NDT_TAB_TILE && base + stride < P.n) barrier_lds_only();
+    // the next batch writes s_pt / s_o again: with Hessian its writes are behind a barrier of the next round; a gradient-only
+    // round writes s_o straight away
+    if (!hess && base + stride < P.n) barrier_lds_only();
   }
 
   LSR_STAMP(2)
@@ -1774,44 +1688,40 @@ int ndt_init_batch(const NdtProblem* src_probs, const NdtState* src_states, NdtP
   return LSR_OK;
 }
 
+// One table-mode dispatch for every workgroup size of a kernel: f receives the NdtTableMode as an integral constant.
+template <class F>
+static int with_table_mode(int tab, F&& f) {
+  switch (tab) {
+    case NDT_TAB_LDS: return f(std::integral_constant<int, NDT_TAB_LDS>{});
+    case NDT_TAB_COMPACT: return f(std::integral_constant<int, NDT_TAB_COMPACT>{});
+    default: return f(std::integral_constant<int, NDT_TAB_DENSE>{});
+  }
+}
+
 template <int NOFF, int TAB, int PTS, bool KD = false>
-static int launch_quad_variant(bool byval, dim3 grid, size_t dyn_lds, hipStream_t stream, const NdtProblem& pv, const NdtProblem* d_probs, int seq) {
-  static bool allowed[2][64] = {};
+static int launch_quad_variant(dim3 grid, size_t dyn_lds, hipStream_t stream, const NdtProblem& pv, int seq) {
+  static bool allowed[64] = {};
   if (dyn_lds > 32 * 1024) {
     int dev = 0;
     LSR_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && !allowed[byval ? 1 : 0][dev]) {
-      const void* fn = byval ? (const void*)ndt_eval_quad_kernel<NOFF, TAB, PTS, true, KD> : (const void*)ndt_eval_quad_kernel<NOFF, TAB, PTS, false, KD>;
-      LSR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NDT_LDS_TABLE_MAX_QUAD));
-      allowed[byval ? 1 : 0][dev] = true;
+    if (dev >= 0 && dev < 64 && !allowed[dev]) {
+      LSR_HIP(hipFuncSetAttribute((const void*)ndt_eval_quad_kernel<NOFF, TAB, PTS, KD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)NDT_LDS_TABLE_MAX_QUAD));
+      allowed[dev] = true;
     }
   }
-  if (byval) hipLaunchKernelGGL((ndt_eval_quad_kernel<NOFF, TAB, PTS, true, KD>), grid, dim3(4 * PTS), dyn_lds, stream, pv, d_probs, seq);
-  else hipLaunchKernelGGL((ndt_eval_quad_kernel<NOFF, TAB, PTS, false, KD>), grid, dim3(4 * PTS), dyn_lds, stream, pv, d_probs, seq);
+  hipLaunchKernelGGL((ndt_eval_quad_kernel<NOFF, TAB, PTS, KD>), grid, dim3(4 * PTS), dyn_lds, stream, pv, seq);
   return LSR_OK;
 }
 
 template <int NOFF, bool KD = false>
-static int launch_quad(const NdtLaunchCfg& cfg, bool byval, dim3 grid, hipStream_t stream, const NdtProblem& pv, const NdtProblem* d_probs, int seq) {
-  const size_t dyn = (cfg.tab == NDT_TAB_LDS || cfg.tab == NDT_TAB_TILE) ? (size_t)cfg.lds_bytes : 0;
-  if (cfg.threads == 64) {  // points per workgroup
-    switch (cfg.tab) {
-      case NDT_TAB_LDS: return launch_quad_variant<NOFF, NDT_TAB_LDS, 64, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-      case NDT_TAB_TILE:   // (never chosen for KDTREE — choose_table_mode —: that form is not instantiated)
-        if constexpr (!KD) return launch_quad_variant<NOFF, NDT_TAB_TILE, 64, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-        else { set_last_error("the tile mode has no KDTREE form"); return LSR_ERR_INVALID_ARGUMENT; }
-      case NDT_TAB_COMPACT: return launch_quad_variant<NOFF, NDT_TAB_COMPACT, 64, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-      default: return launch_quad_variant<NOFF, NDT_TAB_DENSE, 64, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-    }
-  }
-  switch (cfg.tab) {
-    case NDT_TAB_LDS: return launch_quad_variant<NOFF, NDT_TAB_LDS, 128, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-    case NDT_TAB_TILE:   // (never chosen for KDTREE — choose_table_mode —: that form is not instantiated)
-      if constexpr (!KD) return launch_quad_variant<NOFF, NDT_TAB_TILE, 128, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-      else { set_last_error("the tile mode has no KDTREE form"); return LSR_ERR_INVALID_ARGUMENT; }
-    case NDT_TAB_COMPACT: return launch_quad_variant<NOFF, NDT_TAB_COMPACT, 128, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-    default: return launch_quad_variant<NOFF, NDT_TAB_DENSE, 128, KD>(byval, grid, dyn, stream, pv, d_probs, seq);
-  }
+static int launch_quad(const NdtLaunchCfg& cfg, dim3 grid, hipStream_t stream, const NdtProblem& pv, int seq) {
+  const size_t dyn = (cfg.tab == NDT_TAB_LDS) ? (size_t)cfg.lds_bytes : 0;
+  return with_table_mode(cfg.tab, [&](auto tab) {
+    constexpr int TAB = decltype(tab)::value;
+    if (cfg.threads == 64) return launch_quad_variant<NOFF, TAB, 64, KD>(grid, dyn, stream, pv, seq);  // points per workgroup
+    return launch_quad_variant<NOFF, TAB, 128, KD>(grid, dyn, stream, pv, seq);
+  });
 }
 
 template <int NOFF, int TAB, int THREADS, bool SPLIT = false, bool KD = false>
@@ -1839,25 +1749,16 @@ template <int NOFF, bool KD = false>
 static int launch_lane(const NdtLaunchCfg& cfg, bool byval, dim3 grid, hipStream_t stream, const NdtProblem& pv, const NdtProblem* d_probs, int seq) {
   const int tab_bytes = (cfg.tab == NDT_TAB_LDS) ? cfg.lds_bytes : 0;
   const size_t dyn = (size_t)tab_bytes + (size_t)ndt_lane_tile_bytes(cfg.threads);
-  if (cfg.split && cfg.threads == 512 && !KD) {   // two waves per chunk: the 512-thread form only (what single scans use; the KDTREE form has no such variant)
-    switch (cfg.tab) {
-      case NDT_TAB_LDS: return launch_lane_variant<NOFF, NDT_TAB_LDS, 512, true>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-      case NDT_TAB_COMPACT: return launch_lane_variant<NOFF, NDT_TAB_COMPACT, 512, true>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-      default: return launch_lane_variant<NOFF, NDT_TAB_DENSE, 512, true>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-    }
+  if (cfg.split && (KD || cfg.threads != 512)) {   // two waves per chunk: the 512-thread DIRECT form only (what single scans use)
+    set_last_error("lane kernel: the split form takes 512 threads and a DIRECT neighbourhood");
+    return LSR_ERR_INVALID_ARGUMENT;
   }
-  if (cfg.threads == 1024) {
-    switch (cfg.tab) {
-      case NDT_TAB_LDS: return launch_lane_variant<NOFF, NDT_TAB_LDS, 1024, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-      case NDT_TAB_COMPACT: return launch_lane_variant<NOFF, NDT_TAB_COMPACT, 1024, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-      default: return launch_lane_variant<NOFF, NDT_TAB_DENSE, 1024, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-    }
-  }
-  switch (cfg.tab) {
-    case NDT_TAB_LDS: return launch_lane_variant<NOFF, NDT_TAB_LDS, 512, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-    case NDT_TAB_COMPACT: return launch_lane_variant<NOFF, NDT_TAB_COMPACT, 512, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-    default: return launch_lane_variant<NOFF, NDT_TAB_DENSE, 512, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
-  }
+  return with_table_mode(cfg.tab, [&](auto tab) {
+    constexpr int TAB = decltype(tab)::value;
+    if (cfg.split) return launch_lane_variant<NOFF, TAB, 512, true>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
+    if (cfg.threads == 1024) return launch_lane_variant<NOFF, TAB, 1024, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
+    return launch_lane_variant<NOFF, TAB, 512, false, KD>(byval, grid, dyn, stream, pv, d_probs, seq, tab_bytes);
+  });
 }
 
 // Launches seq0 .. seq0+count-1 of the chain (launch seq consumes the bank of launch seq-1).  cfg.max_blocks = grid.x of these
@@ -1871,6 +1772,7 @@ int ndt_launch_evals(const NdtProblem* d_probs, const NdtProblem* h_single, cons
   NdtProblem pv;
   if (byval) pv = *h_single; else std::memset(&pv, 0, sizeof(pv));
   if (cfg.quad) {
+    if (!byval) { set_last_error("the quad kernel takes one registration by value"); return LSR_ERR_INVALID_ARGUMENT; }
     if (cfg.threads != 64 && cfg.threads != 128) { set_last_error("quad kernel: 64 or 128 points per workgroup"); return LSR_ERR_INVALID_ARGUMENT; }
   } else if (cfg.threads != 512 && cfg.threads != 1024) {
     set_last_error("lane kernel: 512 or 1024 threads per workgroup");
@@ -1880,10 +1782,10 @@ int ndt_launch_evals(const NdtProblem* d_probs, const NdtProblem* h_single, cons
     int st;
     if (cfg.quad) {
       switch (cfg.neighborhood) {
-        case LSR_DIRECT1: st = launch_quad<1>(cfg, byval, grid, stream, pv, d_probs, seq0 + i); break;
-        case LSR_KDTREE: st = launch_quad<27, true>(cfg, byval, grid, stream, pv, d_probs, seq0 + i); break;   // the 27 cells + the kd-tree's radius test (NdtProblem::centroid)
-        case LSR_DIRECT26: st = launch_quad<27>(cfg, byval, grid, stream, pv, d_probs, seq0 + i); break;
-        default: st = launch_quad<7>(cfg, byval, grid, stream, pv, d_probs, seq0 + i); break;
+        case LSR_DIRECT1: st = launch_quad<1>(cfg, grid, stream, pv, seq0 + i); break;
+        case LSR_KDTREE: st = launch_quad<27, true>(cfg, grid, stream, pv, seq0 + i); break;   // the 27 cells + the kd-tree's radius test (NdtProblem::centroid)
+        case LSR_DIRECT26: st = launch_quad<27>(cfg, grid, stream, pv, seq0 + i); break;
+        default: st = launch_quad<7>(cfg, grid, stream, pv, seq0 + i); break;
       }
     } else {
       switch (cfg.neighborhood) {

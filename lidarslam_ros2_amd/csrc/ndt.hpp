@@ -44,12 +44,9 @@ constexpr int NDT_NBANKS = 3;                                    // launch seq a
 enum NdtTableMode : int {
   NDT_TAB_DENSE = 0,    // 64-byte records per grid cell in global memory (no cell->slot indirection)
   NDT_TAB_COMPACT = 1,  // cell_slot[] -> compact 64-byte records in global memory (huge grids)
-  NDT_TAB_LDS = 2,      // the whole valid-voxel table (uint16 cell->slot map + 48-byte records) staged into LDS at the
+  NDT_TAB_LDS = 2       // the whole valid-voxel table (uint16 cell->slot map + 48-byte records) staged into LDS at the
                         // head of every launch, in the shadow of the controller: gathers become ds_read_b128
-  NDT_TAB_TILE = 3      // tables that do not fit LDS (ndt_resolution <= 2 m on a 20-frame submap): per workgroup and pass the box
-                        // of dense-table cells its (tile-ordered) points touch is staged into LDS; quad kernel only
 };
-constexpr int NDT_TILE_BYTES = 32 * 1024;  // tile buffer per workgroup: 682 cells of 48 bytes
 
 // cell_slot[cell]: >= 0 the record slot of a leaf lookups can use; -1 no such leaf (empty, fewer than min_points_per_voxel points);
 // -2 - slot a leaf the eigen check invalidated (nr_points = -1).  Every DIRECT lookup tests >= 0.  pclomp's kd-tree holds the latter
@@ -113,7 +110,6 @@ struct NdtProblem {
   int lds_map_bytes;        // NDT_TAB_LDS: bytes of the uint16 cell->slot map at the start of lds_image (multiple of 16)
   const uint4* lds_image;   // NDT_TAB_LDS: [map | records], padded to a multiple of 1 KiB (one wave-wide 16-byte DMA)
   int lds_bytes;
-  int tile_bytes;           // NDT_TAB_TILE: capacity of the per-workgroup LDS tile buffer (dynamic LDS of the launch)
   long long* bins;          // [NDT_NBANKS][NDT_NSHARDS][NDT_NBINS][32] int64 accumulators (zeroed before launch 0)
   NdtState* st;             // [2] double buffered by launch parity
   NdtMailbox* mailbox;      // device view of the host mailbox (single registrations fed by polling) or nullptr
@@ -152,17 +148,16 @@ struct NdtLaunchCfg {
   int tab = NDT_TAB_DENSE; // NdtTableMode
   int threads = NDT_LANE_THREADS;  // lane kernel: threads per workgroup (512 / 1024); quad kernel: POINTS per workgroup (64 / 128)
   int lds_bytes = 0;       // dynamic LDS (largest lds_bytes of the batch) when tab == NDT_TAB_LDS
-  int sorted = 0;          // 1: the problems read the tile-ordered copy of the source (ndt_sort_source)
-  int split = 0;           // lane kernel, 512 threads: 1 = two waves per chunk (each forms one half of the per-point tree): single scans
-                           // that leave the chip half empty with one lane per point (cfg 5).  Same bits.
-  int quad = 0;            // 1: four lanes per source point, 512-thread workgroups (single registrations: spreads a 30k-point scan
-                           // over every CU; batches whose tables need NDT_TAB_TILE); 0: the lane kernel, one lane per point
-                           // (candidate sets, large single scans).  Both return the same bits (canon:: in ndt.hip).
+  int split = 0;           // lane kernel, 512 threads, DIRECT neighbourhoods: 1 = two waves per chunk (each forms one half of the
+                           // per-point tree): single scans that leave the chip half empty with one lane per point (cfg 5).  Same bits.
+  int quad = 0;            // 1: four lanes per source point, 512-thread workgroups (single registrations only, batch == 1: spreads
+                           // a 30k-point scan over every CU); 0: the lane kernel, one lane per point (candidate sets, large
+                           // single scans).  Both return the same bits (canon:: in ndt.hip).
 };
 constexpr int NDT_QUAD_THREADS = 512;
 constexpr int NDT_QUAD_POINTS = NDT_QUAD_THREADS / 4;  // source points per workgroup pass
 // Launch `count` chained derivative+controller passes.
-// h_single (nullable): host copy of the problem, passed by value when batch == 1.
+// h_single (nullable): host copy of the problem, passed by value when batch == 1 (the quad kernel has no other form).
 int ndt_launch_evals(const NdtProblem* d_probs, const NdtProblem* h_single, const NdtLaunchCfg& cfg, int seq0, int count,
                      hipStream_t stream);
 // ---- batched builds (candidate sets, graph_based_slam_component.cpp:181-231 generalised): the per-member parameters of up to
@@ -199,10 +194,6 @@ int ndt_grid_geometry(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, 
 constexpr int VG_DENSE_MAX_CELLS = 16383;   // beyond: radix sort.  (A two-wave form with 32-bit packed counters for up to 36 000 cells was
                                             // built and measured on cfg 5's 22 113-cell grid: 0.33-0.35 ms against the radix sort's 0.30 — every
                                             // 4096-point workgroup clears, writes and prefixes a 22k-entry table; removed.)
-// Order the source cloud by voxel tile (NDT_TAB_TILE): counting sort of the points by the Morton code of the 2^shift x 2^shift
-// column of grid cells their guess-moved image falls into (grid_dense.hip).  Consecutive points of `out` are neighbours in
-// space, so the cells a workgroup of the derivative pass touches form a small box.  T12: row-major 3x4 guess (host memory).
-int ndt_sort_source(const DeviceCloud& src, const float* T12, const VoxelGridDev& grid, DeviceCloud& out, BuildScratch& sc, hipStream_t stream);
 // One small launch that writes the initial state (passed in the kernel arguments) into both state buffers and clears the
 // quad kernel's accumulator banks (d_bins nullable).
 int ndt_init_single(const NdtState& st, NdtState* d_state2, long long* d_bins, hipStream_t stream);

@@ -309,6 +309,43 @@ def test_launch_variants_agree_with_each_other(case, neighborhood):
         assert np.array_equal(aligned[v][0], aligned[VARIANTS[0]][0]) and aligned[v][1:] == aligned[VARIANTS[0]][1:], v
 
 
+def test_tuning_keys_name_only_forms_that_exist(case):
+    """The retired tile table mode (3) and source-ordering key (45) are refused as invalid arguments, the table modes -1 .. 2 are
+    still taken, and a KDTREE registration with the split form forced (the KDTREE kernels have none: the launch configuration
+    falls back to one wave per chunk) returns the bits of VARIANTS[0]."""
+    import ctypes as C
+
+    import lidarslam_ros2_amd as L
+    from lidarslam_ros2_amd import _capi
+
+    ndt = make_ndt(5.0)
+    with pytest.raises(_capi.RegistrationError) as ei:
+        ndt.setTuning(table_mode=3)
+    assert ei.value.status == -1 and "-1 .. 2" in str(ei.value)   # LSR_ERR_INVALID_ARGUMENT, names the valid range
+    lib, got = _capi.load(), C.c_int32(0)
+    assert lib.lsr_set_i32(ndt._h, 45, 0) == -1 and lib.lsr_set_i32(ndt._h, 45, 1) == -1
+    assert lib.lsr_get_i32(ndt._h, 45, C.byref(got)) == -1
+    for mode in (-1, 0, 1, 2):
+        ndt.setTuning(table_mode=mode)
+        assert lib.lsr_get_i32(ndt._h, _capi.NDT_TABLE_MODE, C.byref(got)) == 0 and got.value == mode
+
+    def run(tune):
+        r = make_ndt(5.0)
+        r.setNeighborhoodSearchMethod(L.KDTREE)
+        tune(r)
+        r.setInputTarget(synth.as_pointxyzi(case.target))
+        r.setInputSource(synth.as_pointxyzi(case.source))
+        d = [r.derivatives(np.r_[0.3, -0.2, 0.05, 0.01, -0.015, 0.02], compute_hessian=h) for h in (True, False)]
+        r.align(case.guess)
+        return d, r.getFinalTransformation(), r.getFinalNumIteration(), r.last_result["n_evaluations"]
+
+    ref = run(lambda r: _tune(r, VARIANTS[0]))
+    forced = run(lambda r: r.setTuning(quad=0, workgroup=512, split=1))
+    for (s, g, H), (s0, g0, H0) in zip(forced[0], ref[0]):
+        assert s == s0 and np.array_equal(g, g0) and np.array_equal(H, H0)
+    assert np.array_equal(forced[1], ref[1]) and forced[2:] == ref[2:]
+
+
 @pytest.mark.parametrize("res", [5.0, 3.0])
 def test_counting_sort_builder_equals_radix_sort_builder(case, res):
     """K1/K2 by the counting-sort builder (dense key spaces) and by the radix-sort builder: identical voxel set, counts and

@@ -12,5 +12,4 @@ run ndt_quad0 LSR_NDT_QUAD=0
 run wait_sleep LSR_WAIT_MODE=sleep
 run wait_yield LSR_WAIT_MODE=yield
 run table_dense LSR_NDT_TABLE_MODE=0
-run table_tile LSR_NDT_TABLE_MODE=3
 run ndt_lane512 LSR_NDT_QUAD=0 LSR_NDT_WORKGROUP=512
