@@ -99,10 +99,14 @@ typedef enum lsr_key {
                                          one for the leaf count), 2 = on the device (one wait: from the second
                                          lsr_set_input_source_pc2 / _frontend of an object on), 3 = the device form came back
                                          flagged (more key bits than planned, or an index overflow) and the host form ran */
-  LSR_NDT_SPLIT = 47                  /* single NDT registrations on the 512-thread lane kernel: 1 = two waves per 64-point chunk (each
+  LSR_NDT_SPLIT = 47,                 /* single NDT registrations on the 512-thread lane kernel: 1 = two waves per 64-point chunk (each
                                          forms one half of the per-point neighbour tree; half the serial chain per wave, twice the waves),
                                          0 = one wave per chunk, -1 = automatic (= 0: measured on BASELINE cfg 5, the split form is not
                                          faster — the pass is bound by its fixed latency chain).  Environment preset LSR_NDT_SPLIT */
+  LSR_TARGET_PREPARED = 48            /* read-only (lsr_get_i32): 1 = an align with this object's parameters finds nothing left to build on
+                                         the current target (GICP: neighbour grid and k-NN covariances computed with this object's
+                                         k_correspondences / gicp_epsilon; NDT: voxel grid at this object's resolution), 0 = the next
+                                         align builds something first, or there is no target */
 } lsr_key;
 /* Environment presets read when an object is created: LSR_NDT_WORKGROUP, LSR_NDT_TABLE_MODE, LSR_NDT_QUAD, LSR_GRID_BUILDER,
  * LSR_WAIT_MODE (the keys above); LSR_NDT_CHAINS=1|2|3 fixes the number of independent launch chains a candidate set runs as (default: two
@@ -181,6 +185,25 @@ int lsr_wait_stream(lsr_handle h, void* producer_stream);
  * pointers (keyframes kept resident in HBM); the assembled target never visits the host. */
 int lsr_set_input_target_frames(lsr_handle h, int n_frames, const void* const* frames, const size_t* counts, size_t stride_bytes,
                                 const float* poses16, int on_device);
+/* The same followed by pcl::VoxelGrid(leaf) of the assembled cloud and setInputTarget of the FILTERED cloud, all in HBM: the
+ * GICP branch of a map update (scanmatcher_component.cpp:308-316: `targeted_cloud_`, assembled newest keyframe first by
+ * :448-464, goes through VoxelGrid(vg_size_for_input) before setInputTarget).  The filtered cloud is, bit for bit, what
+ * lsr_voxel_grid_filter returns for the same assembled points (centroid per leaf, float sums in cloud order, output in
+ * leaf-index order) — so the order of the frames matters for the bits.  Any method: a GICP object gets its neighbour grid,
+ * an NDT object its voxel grid over the filtered cloud.  n_out (nullable) receives the number of target points.
+ * leaf <= 0 is LSR_ERR_INVALID_ARGUMENT; on error the object keeps no target.  The window is assembled by one launch that also
+ * leaves the bounding box of the assembled cloud on the device: from the object's second call on the filter works out its grid
+ * dimensions there (LSR_VOXEL_FILTER_FORM 2, one host wait). */
+int lsr_set_input_target_frames_filtered(lsr_handle h, int n_frames, const void* const* frames, const size_t* counts,
+                                         size_t stride_bytes, const float* poses16, int on_device, float leaf, size_t* n_out);
+/* Builds now, on the object's stream, everything the first lsr_align against the current target would still have to build, and
+ * returns after it has completed; needs no input source.  GICP: the neighbour grid and the k-NN covariances of the target with
+ * the object's current k_correspondences / gicp_epsilon (the reference computes them lazily inside align).  NDT: nothing is
+ * left as a rule (setInputTarget builds the voxel grid).  LSR_ERR_NO_TARGET without a target, LSR_ERR_TOO_FEW_POINTS when the
+ * target has fewer points than k_correspondences.  Called on the object that built a target before lsr_share_target hands it
+ * over, the scan that takes the target over pays for no target-side build (LSR_TARGET_PREPARED reads 1 on the taker when its
+ * k_correspondences / gicp_epsilon are the builder's). */
+int lsr_prepare_target(lsr_handle h);
 /* registration_->setInputSource(cloud)   scanmatcher_component.cpp:329; graph_based_slam_component.cpp:181 */
 int lsr_set_input_source(lsr_handle h, const void* pts, size_t stride_bytes, size_t n);
 int lsr_set_input_source_device(lsr_handle h, const void* dev_pts, size_t stride_bytes, size_t n);

@@ -19,7 +19,7 @@ KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
 (RESOLUTION, TRANSFORMATION_EPSILON, STEP_SIZE, OUTLIER_RATIO, MAX_CORRESPONDENCE_DISTANCE, ROTATION_EPSILON,
  EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON) = range(8)
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
- HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT) = range(32, 48)
+ HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED) = range(32, 49)
 
 EXPORTED_SYMBOLS = [
     "lsr_version", "lsr_status_string", "lsr_last_error", "lsr_device_count", "lsr_create", "lsr_destroy",
@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "lsr_debug_angle_tables", "lsr_set_input_source_pc2", "lsr_get_source_pc2", "lsr_voxel_grid_filter_pc2", "lsr_shard_range", "lsr_comm_unique_id", "lsr_comm_create", "lsr_comm_destroy", "lsr_align_batch_sharded",
     "lsr_shard_plan", "lsr_align_batch_planned", "lsr_align_fitness_batch",
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
-    "lsr_comm_all_gather_records",
+    "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target",
 ]
 
 
@@ -112,6 +112,9 @@ def load() -> C.CDLL:
     L.lsr_share_target.argtypes = [vp, vp]
     L.lsr_wait_stream.argtypes = [vp, vp]
     L.lsr_set_input_target_frames.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, fp, C.c_int]
+    L.lsr_set_input_target_frames_filtered.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, fp, C.c_int, C.c_float,
+                                                       C.POINTER(C.c_size_t)]
+    L.lsr_prepare_target.argtypes = [vp]
     L.lsr_set_input_source_filtered.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_set_input_source_frontend.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_double, C.c_double, C.c_float, C.c_int,
                                                 C.POINTER(C.c_size_t)]

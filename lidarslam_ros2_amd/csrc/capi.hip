@@ -986,6 +986,11 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_GRID_BUILDER: *v = h->scratch.force_sort_path ? 1 : 0; return LSR_OK;
     case LSR_WAIT_MODE: *v = h->scratch.wait_mode; return LSR_OK;
     case LSR_VOXEL_FILTER_FORM: *v = h->scratch.vg_form; return LSR_OK;
+    case LSR_TARGET_PREPARED:
+      if (h->method == LSR_METHOD_GICP) *v = gicp_target_prepared(h) ? 1 : 0;
+      else *v = (h->target && h->target->n > 0 && h->target->has_grid && h->target->grid_leaf == (float)h->ndt.resolution &&
+                 (h->ndt.neighborhood != LSR_KDTREE || h->target->has_centroids || h->target->grid.ncells == 0)) ? 1 : 0;
+      return LSR_OK;
     default: set_last_error("unknown i32 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -1061,6 +1066,75 @@ int lsr_set_input_target_frames(lsr_handle h, int n_frames, const void* const* f
   h->target = t;
   st = (h->method == LSR_METHOD_NDT) ? ensure_ndt_grid(h) : ensure_target_hash(h);
   if (st) { h->target.reset(); return st; }
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  return LSR_OK;
+}
+
+// The GICP branch of a map update (scanmatcher_component.cpp:308-316,448-464): window -> pcl::VoxelGrid -> setInputTarget, in HBM.
+// The window is assembled by ONE launch that also leaves its bounding-box records behind (assemble_frames_bbox), so the filter
+// behind it starts without a bounding-box pass and, from the object's second update on, without a host wait for the dimensions.
+int lsr_set_input_target_frames_filtered(lsr_handle h, int n_frames, const void* const* frames, const size_t* counts, size_t stride_bytes,
+                                         const float* poses16, int on_device, float leaf, size_t* n_out) {
+  LSR_CHECK_HANDLE(h);
+  if (n_out) *n_out = 0;
+  h->target.reset();   // on error the object keeps no target
+  if (n_frames <= 0 || !frames || !counts || !poses16 || stride_bytes < 12 || (stride_bytes % 4)) {
+    set_last_error("bad frame list");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  if (!(leaf > 0)) { set_last_error("leaf size must be > 0"); return LSR_ERR_INVALID_ARGUMENT; }
+  size_t total = 0;
+  for (int f = 0; f < n_frames; f++) {
+    if (counts[f] > 0 && !frames[f]) { set_last_error("null frame pointer"); return LSR_ERR_INVALID_ARGUMENT; }
+    total += counts[f];
+  }
+  if (total > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
+  int st;
+  if ((st = h->h_frames.reserve((size_t)n_frames))) return st;
+  if ((st = h->d_frames.reserve((size_t)n_frames))) return st;
+  if (!on_device && (st = h->staging.reserve(total * stride_bytes))) return st;
+  std::vector<int> first_slice((size_t)n_frames);
+  const int n_slices = frames_slice_count(counts, n_frames, first_slice.data());
+  // whatever was enqueued has finished before the call returns: the table, the staged frames and the caller's buffers are free again
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{h->stream};
+  size_t off = 0;
+  for (int f = 0; f < n_frames; f++) {   // host frames are staged back to back and go through the same launch
+    FrameSlot& F = h->h_frames.p[f];
+    F.records = static_cast<const unsigned char*>(frames[f]);
+    if (!on_device) {
+      F.records = h->staging.p + off * stride_bytes;
+      if (counts[f] > 0) LSR_HIP(hipMemcpyAsync(h->staging.p + off * stride_bytes, frames[f], counts[f] * stride_bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    F.count = (int)counts[f];
+    F.first_out = (int)off;
+    F.first_slice = first_slice[f];
+    F.pad = 0;
+    std::memcpy(F.T16, poses16 + 16 * (size_t)f, sizeof(float) * 16);
+    off += counts[f];
+  }
+  LSR_HIP(hipMemcpyAsync(h->d_frames.p, h->h_frames.p, sizeof(FrameSlot) * (size_t)n_frames, hipMemcpyHostToDevice, h->stream));
+  if ((st = assemble_frames_bbox(h->d_frames.p, n_frames, n_slices, stride_bytes, total, h->raw, h->scratch, h->stream))) return st;
+  auto t = fresh_target(h);
+  if ((st = voxel_grid_filter(h->raw, leaf, t->cloud, h->scratch, h->stream))) return st;
+  t->n = t->cloud.n;
+  h->target = t;
+  st = (h->method == LSR_METHOD_NDT) ? ensure_ndt_grid(h) : ensure_target_hash(h);
+  if (st) { h->target.reset(); return st; }
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  if (n_out) *n_out = t->n;
+  return LSR_OK;
+}
+
+// Everything the first align against the current target would still have to build, now (the map thread's object, before the
+// hand-over: lsr_share_target then passes a target on that the callback thread's next scan only reads).
+int lsr_prepare_target(lsr_handle h) {
+  LSR_CHECK_HANDLE(h);
+  if (!h->target || h->target->n == 0) { set_last_error("prepare before setInputTarget"); return LSR_ERR_NO_TARGET; }
+  if (h->method == LSR_METHOD_GICP) return gicp_prepare_target(h);
+  // NDT: setInputTarget built the voxel grid (pclomp's init()), so as a rule nothing is left; a resolution or neighbourhood
+  // method set since then is served here as the next align would serve it
+  int st = ensure_ndt_grid(h);
+  if (st) return st;
   LSR_HIP(hipStreamSynchronize(h->stream));
   return LSR_OK;
 }

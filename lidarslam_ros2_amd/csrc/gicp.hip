@@ -1243,10 +1243,12 @@ int compute_covariances(lsr_handle_s* h, const DeviceCloud& cloud, const HashGri
 // inside the first two fine shells (the 1-NN correspondence grid stays at 0.5 m).
 constexpr float GICP_COV_CELL = 1.0f;
 
-int ensure_covariances(lsr_handle_s* h) {
+// The target half: neighbour grid + k-NN covariances with this object's k_correspondences / gicp_epsilon.  Needs no source
+// (lsr_prepare_target runs it on the object that built the target, before the hand-over).
+int ensure_target_covariances(lsr_handle_s* h) {
   TargetData& t = *h->target;
   int st;
-  if ((int)t.n < h->gicp.k || (int)h->source.n < h->gicp.k) {
+  if ((int)t.n < h->gicp.k) {
     set_last_error("GICP: cloud has fewer points than k_correspondences");
     return LSR_ERR_TOO_FEW_POINTS;
   }
@@ -1268,7 +1270,16 @@ int ensure_covariances(lsr_handle_s* h) {
     t.cov_eps = h->gicp.gicp_eps;
     h->source_cov_valid = false;
   }
-  lock.unlock();
+  return LSR_OK;
+}
+
+int ensure_covariances(lsr_handle_s* h) {
+  int st;
+  if ((int)h->target->n < h->gicp.k || (int)h->source.n < h->gicp.k) {
+    set_last_error("GICP: cloud has fewer points than k_correspondences");
+    return LSR_ERR_TOO_FEW_POINTS;
+  }
+  if ((st = ensure_target_covariances(h))) return st;
   if (!h->source_cov_valid) {
     if ((st = nn_build_hash(h->source, GICP_COV_CELL, h->source_hash, h->scratch, h->stream))) return st;
     if ((st = compute_covariances(h, h->source, h->source_hash, h->source_cov))) return st;
@@ -1278,6 +1289,20 @@ int ensure_covariances(lsr_handle_s* h) {
 }
 
 }  // namespace
+
+int gicp_prepare_target(lsr_handle_s* h) {
+  if (!h->target || h->target->n == 0) { set_last_error("prepare before setInputTarget"); return LSR_ERR_NO_TARGET; }
+  int st = ensure_target_covariances(h);
+  if (st) return st;
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  return LSR_OK;
+}
+
+bool gicp_target_prepared(const lsr_handle_s* h) {
+  if (!h->target || h->target->n == 0) return false;
+  const TargetData& t = *h->target;
+  return t.has_hash && t.has_cov && t.cov_k == h->gicp.k && t.cov_eps == h->gicp.gicp_eps;
+}
 
 int gicp_get_covariances(lsr_handle_s* h, int which, double* cov) {
   if (!h->target || h->target->n == 0) return LSR_ERR_NO_TARGET;

@@ -49,4 +49,8 @@ int gicp_align(lsr_handle_s* h, const float* guess, float* final_T, lsr_result* 
 // B registrations side by side (each chain on its own object's stream, one host loop feeding them all)
 int gicp_align_batch(lsr_handle_s* const* hs, int B, const float* guesses, float* finals, lsr_result* results);
 int gicp_get_covariances(lsr_handle_s* h, int which, double* cov);
+// lsr_prepare_target: neighbour grid + k-NN covariances of the current target on h's stream, complete on return (no source needed)
+int gicp_prepare_target(lsr_handle_s* h);
+// nothing of the current target is left for an align with h's k_correspondences / gicp_epsilon to build
+bool gicp_target_prepared(const lsr_handle_s* h);
 }  // namespace lsr

@@ -77,6 +77,8 @@ struct lsr_handle_s {
   unsigned int align_token = 0;
   DevBuf<float> d_T16;
   DevBuf<float> d_poses;  // N2: keyframe poses
+  DevBuf<lsr::FrameSlot> d_frames;   // N2, one-launch assembly: the window's frame table ...
+  PinBuf<lsr::FrameSlot> h_frames;   // ... and the pinned copy it is uploaded from
 
   GicpWorkspace gicp_ws;
 

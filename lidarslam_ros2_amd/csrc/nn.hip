@@ -559,6 +559,13 @@ __global__ __launch_bounds__(256) void fitness_final_group_kernel(const FitGroup
 // moved by its pose); graph_based_slam/src/graph_based_slam_component.cpp:208-222 (loop candidate window).
 // fp32 arithmetic in the reference's order ((m00*x + m01*y) + m02*z) + m03, no FMA contraction (this TU).
 namespace {
+// one point of a keyframe moved by its pose: the arithmetic both assembly kernels share (their results are the same bits)
+__device__ __forceinline__ void frame_point_rn(const float* __restrict__ T16, float x, float y, float z, float& qx, float& qy, float& qz) {
+  qx = xform_rn(T16[0], T16[4], T16[8], T16[12], x, y, z);
+  qy = xform_rn(T16[1], T16[5], T16[9], T16[13], x, y, z);
+  qz = xform_rn(T16[2], T16[6], T16[10], T16[14], x, y, z);
+}
+
 __global__ __launch_bounds__(256) void transform_append_kernel(const unsigned char* __restrict__ aos, size_t stride, int n,
                                                                const float* __restrict__ T16, float* __restrict__ ox,
                                                                float* __restrict__ oy, float* __restrict__ oz) {
@@ -566,9 +573,88 @@ __global__ __launch_bounds__(256) void transform_append_kernel(const unsigned ch
   if (i >= n) return;
   const float* p = (const float*)(aos + (size_t)i * stride);
   const float x = p[0], y = p[1], z = p[2];
-  ox[i] = xform_rn(T16[0], T16[4], T16[8], T16[12], x, y, z);
-  oy[i] = xform_rn(T16[1], T16[5], T16[9], T16[13], x, y, z);
-  oz[i] = xform_rn(T16[2], T16[6], T16[10], T16[14], x, y, z);
+  frame_point_rn(T16, x, y, z, ox[i], oy[i], oz[i]);
+}
+
+// The whole window in ONE launch, with the bounding box of what it wrote (lsr_set_input_target_frames_filtered).  The frames are
+// cut into slices of FRAME_SLICE points; a workgroup walks the slices blockIdx.x, blockIdx.x + gridDim.x, ... (at most
+// BBOX_MAX_PARTS workgroups: one bounding-box record each), finds the frame of a slice in the table (uniform: scalar loads) and
+// keeps four records per lane in flight — lane l of trip u reads record 256 u + l of the slice, so a wave's loads cover
+// consecutive 32-byte records.  The min / max / count of the finite points are folded across the wave by shuffles first; LDS
+// sees four rows per workgroup.  The records go where pc2_ingest_kernel puts a scan's: device memory (voxel_grid_filter's
+// device-side dimensions) and the host mailbox (cloud_bbox_end), one self-validating 8-byte granule each.
+constexpr int FRAME_SLICE = 1024;
+__global__ __launch_bounds__(256) void assemble_frames_bbox_kernel(const FrameSlot* __restrict__ frames, int n_frames, int n_slices,
+                                                                   size_t stride, float* __restrict__ ox, float* __restrict__ oy,
+                                                                   float* __restrict__ oz, unsigned long long* __restrict__ parts_dev,
+                                                                   BuildMailbox* __restrict__ mb, unsigned int token) {
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  unsigned int cnt = 0;
+  const int tid = threadIdx.x;
+  for (int sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
+    int lo = 0, hi = n_frames - 1;   // the last frame whose first slice is <= sl (frames without points own no slice)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (frames[mid].first_slice <= sl) lo = mid; else hi = mid - 1;
+    }
+    const FrameSlot& F = frames[lo];
+    const unsigned char* __restrict__ rec = F.records;
+    const int count = F.count, base = (sl - F.first_slice) * FRAME_SLICE;
+    const size_t out0 = (size_t)F.first_out;
+    const bool wide = ((stride & 15) == 0) && ((reinterpret_cast<size_t>(rec) & 15) == 0);   // one 16-byte load per record
+    float p[4][3];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = base + u * 256 + tid;
+      if (i < count) {
+        if (wide) {
+          const float4 q = *reinterpret_cast<const float4*>(rec + (size_t)i * stride);
+          p[u][0] = q.x; p[u][1] = q.y; p[u][2] = q.z;
+        } else {
+          const float* q = reinterpret_cast<const float*>(rec + (size_t)i * stride);
+          p[u][0] = q[0]; p[u][1] = q[1]; p[u][2] = q[2];
+        }
+      } else {
+        p[u][0] = p[u][1] = p[u][2] = NAN;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = base + u * 256 + tid;
+      if (i >= count) continue;
+      float q[3];
+      frame_point_rn(F.T16, p[u][0], p[u][1], p[u][2], q[0], q[1], q[2]);
+      ox[out0 + i] = q[0]; oy[out0 + i] = q[1]; oz[out0 + i] = q[2];
+      if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) continue;
+      cnt++;
+#pragma unroll
+      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], q[k]); mx[k] = fmaxf(mx[k], q[k]); }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64)); }
+    cnt += __shfl_xor(cnt, m, 64);
+  }
+  __shared__ float s_mn[4][3], s_mx[4][3];
+  __shared__ unsigned int s_cnt[4];
+  const int wv = tid >> 6;
+  if ((tid & 63) == 0) {
+    for (int k = 0; k < 3; k++) { s_mn[wv][k] = mn[k]; s_mx[wv][k] = mx[k]; }
+    s_cnt[wv] = cnt;
+  }
+  __syncthreads();
+  if (tid < BBOX_GRANULES) {
+    const int k = tid;
+    unsigned int bits;
+    if (k < 3) bits = __float_as_uint(fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k])));
+    else if (k < 6) bits = __float_as_uint(fmaxf(fmaxf(s_mx[0][k - 3], s_mx[1][k - 3]), fmaxf(s_mx[2][k - 3], s_mx[3][k - 3])));
+    else bits = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const unsigned long long g = ((unsigned long long)token << 32) | bits;
+    parts_dev[(size_t)blockIdx.x * 8 + k] = g;
+    __hip_atomic_store(&mb->part[blockIdx.x].g[k], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
 }
 }  // namespace
 
@@ -578,6 +664,34 @@ int transform_append(const void* d_aos, size_t stride_bytes, size_t n, const flo
   hipLaunchKernelGGL(transform_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                      (const unsigned char*)d_aos, stride_bytes, (int)n, d_T16, out.x() + offset, out.y() + offset, out.z() + offset);
   LSR_HIP(hipGetLastError());
+  return LSR_OK;
+}
+
+int frames_slice_count(const size_t* counts, int n_frames, int* first_slice /*nullable: [n_frames]*/) {
+  long slices = 0;
+  for (int f = 0; f < n_frames; f++) {
+    if (first_slice) first_slice[f] = (int)slices;
+    slices += (long)((counts[f] + FRAME_SLICE - 1) / FRAME_SLICE);
+  }
+  return (int)slices;
+}
+
+int assemble_frames_bbox(const FrameSlot* d_frames, int n_frames, int n_slices, size_t stride_bytes, size_t total, DeviceCloud& out,
+                         BuildScratch& sc, hipStream_t stream) {
+  int st = out.resize(total);
+  if (st) return st;
+  if (total == 0 || n_slices <= 0) return LSR_OK;
+  if ((st = sc.ensure_mailbox())) return st;
+  if ((st = sc.bbox_dev.reserve((size_t)BBOX_MAX_PARTS * 8))) return st;
+  unsigned int token = ++sc.token;
+  if (token == 0) token = ++sc.token;
+  const int nb = std::min(n_slices, BBOX_MAX_PARTS);
+  hipLaunchKernelGGL(assemble_frames_bbox_kernel, dim3(nb), dim3(256), 0, stream, d_frames, n_frames, n_slices, stride_bytes, out.x(), out.y(),
+                     out.z(), sc.bbox_dev.p, sc.d_mb, token);
+  LSR_HIP(hipGetLastError());
+  sc.bbox_parts = nb;
+  sc.bbox_token = token;
+  out.bbox_enqueued = true;
   return LSR_OK;
 }
 

@@ -9,6 +9,20 @@ namespace lsr {
 // N2: transform one keyframe (strided xyz, device) by a column-major 4x4 and write it at `offset` of `out`.
 int transform_append(const void* d_aos, size_t stride_bytes, size_t n, const float* d_T16, DeviceCloud& out, size_t offset,
                      hipStream_t stream);
+// The same for a whole window in one launch (lsr_set_input_target_frames_filtered): one table entry per frame, device resident.
+// The launch also leaves the bounding-box records of the assembled cloud where pc2_ingest leaves a scan's (sc.bbox_dev, the host
+// mailbox; out.bbox_enqueued), so the voxel_grid_filter behind it needs no bounding-box pass and can take its device-side form.
+struct FrameSlot {
+  const unsigned char* records;   // strided xyz records (device)
+  int count;                      // points of the frame
+  int first_out;                  // index of its first point in the assembled cloud
+  int first_slice;                // index of its first slice (frames_slice_count)
+  int pad;
+  float T16[16];                  // column-major pose
+};
+int frames_slice_count(const size_t* counts, int n_frames, int* first_slice);
+int assemble_frames_bbox(const FrameSlot* d_frames, int n_frames, int n_slices, size_t stride_bytes, size_t total, DeviceCloud& out,
+                         BuildScratch& sc, hipStream_t stream);
 float nn_pick_cell(size_t n, const lsr_handle_s* h);
 int nn_build_hash(const DeviceCloud& cloud, float cell, HashGridDev& grid, BuildScratch& sc, hipStream_t stream);
 // the same structure for NDT targets whose voxel grid was built by the counting-sort builder: a refinement of the voxel order

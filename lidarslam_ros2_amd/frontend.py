@@ -8,6 +8,8 @@ tests/test_frontend_stream_gpu.py) and — through an adapter with the same meth
     every trans_for_mapupdate m  (updateMap) VoxelGrid(vg_size_for_map) of the scan (:442-446), kept with the registered pose as the newest
                                  submap (:466-478); target = that scan + the num_targeted_cloud - 1 submaps before it, each moved by its
                                  pose and concatenated (:448-464); setInputTarget at the start of the next callback (:304-307)
+    registration_method "GICP"   the same loop; the assembled window is put through VoxelGrid(vg_size_for_input) before setInputTarget
+                                 (:308-316): setInputTargetFramesFiltered + prepareTarget (the target's covariances) on the map side
 
 Nothing here computes: every step is one call into the registration object.
 
@@ -58,6 +60,7 @@ class FrontendParams:   # scanmatcher_component.cpp:36-60 (declare_parameter def
     scan_min_range: float = 0.1
     scan_max_range: float = 100.0
     num_targeted_cloud: int = 10
+    registration_method: str = "NDT"   # :98-125 — "NDT" or "GICP"
 
 
 @dataclass
@@ -81,6 +84,8 @@ class FrontendReplay:
                  swap_lag: int = 0):
         self.reg = reg
         self.p = params or FrontendParams()
+        if self.p.registration_method not in ("NDT", "GICP"):
+            raise ValueError("registration_method must be \"NDT\" or \"GICP\" (scanmatcher_component.cpp:121-124)")
         self.to_device = to_device or (lambda a: a)
         # `mapper` (optional): a second registration object whose input-source slot serves as the map side's filter — with it and a
         # device-resident payload the new keyframe (range filter + VoxelGrid(vg_size_for_map)) is produced and kept in HBM
@@ -122,7 +127,16 @@ class FrontendReplay:
     def _set_target(self):
         # newest first, as updateMap concatenates (:448-464); the voxel grid does not depend on the order
         window = self.submaps[-self.p.num_targeted_cloud:][::-1]
-        (self.builder or self.reg).setInputTargetFrames([w[0] for w in window], [w[1] for w in window])
+        obj = self.builder or self.reg
+        if self.p.registration_method == "GICP":
+            # the GICP branch (:308-316): the assembled window goes through VoxelGrid(vg_size_for_input) before setInputTarget (here
+            # the order does matter: it is the order of the filter's float sums), and what the reference's first align against the new
+            # target would compute lazily — the target's k-NN covariances — is built here, on the object and the thread that built the
+            # target, so that the hand-over stays a pointer swap and the scan that takes the target over registers like any other
+            obj.setInputTargetFramesFiltered([w[0] for w in window], [w[1] for w in window], self.p.vg_size_for_input)
+            obj.prepareTarget()
+            return
+        obj.setInputTargetFrames([w[0] for w in window], [w[1] for w in window])
 
     def _hand_over(self):
         if self.builder is not None:

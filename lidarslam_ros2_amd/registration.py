@@ -140,9 +140,8 @@ class Registration:
         capi.check(fn(self._h, p, stride, n), "setInputTarget")
         self._keep["target"] = None  # the core keeps its own SoA copy in HBM
 
-    def setInputTargetFrames(self, frames, poses):
-        """Submap assembly on the device: frame f transformed by poses[f] (4x4), concatenated, then
-        setInputTarget (scanmatcher_component.cpp:449-464,307).  Frames: host arrays or CUDA tensors, same layout."""
+    def _frame_args(self, frames, poses):
+        """-> (n_frames, pointers, counts, stride, poses as (n,16) fp32 column-major, on_device, keepalive)."""
         args = [_cloud_args(f) for f in frames]
         dev_frames = [a[4] for a in args if _is_torch_cuda(a[4])]
         if dev_frames:
@@ -154,10 +153,37 @@ class Registration:
         ptrs = (C.c_void_p * nf)(*[a[0] for a in args])
         counts = (C.c_size_t * nf)(*[a[2] for a in args])
         P = np.ascontiguousarray(np.stack([_mat_to_col16(p) for p in poses]), np.float32)
-        capi.check(self._lib.lsr_set_input_target_frames(self._h, nf, ptrs, counts, args[0][1],
+        return nf, ptrs, counts, args[0][1], P, dev, args
+
+    def setInputTargetFrames(self, frames, poses):
+        """Submap assembly on the device: frame f transformed by poses[f] (4x4), concatenated, then
+        setInputTarget (scanmatcher_component.cpp:449-464,307).  Frames: host arrays or CUDA tensors, same layout."""
+        nf, ptrs, counts, stride, P, dev, args = self._frame_args(frames, poses)
+        capi.check(self._lib.lsr_set_input_target_frames(self._h, nf, ptrs, counts, stride,
                                                          P.ctypes.data_as(C.POINTER(C.c_float)), 1 if dev else 0),
                    "setInputTargetFrames")
         self._n_target = int(sum(a[2] for a in args))
+
+    def setInputTargetFramesFiltered(self, frames, poses, leaf: float) -> int:
+        """The same followed by pcl::VoxelGrid(leaf) of the assembled cloud; the FILTERED cloud becomes the target — the GICP branch of
+        a map update (scanmatcher_component.cpp:308-316,448-464), all in HBM.  The frames' order (newest first in the frontend) decides
+        the float sums' order, hence the bits.  Returns the number of target points."""
+        nf, ptrs, counts, stride, P, dev, args = self._frame_args(frames, poses)
+        n_out = C.c_size_t()
+        capi.check(self._lib.lsr_set_input_target_frames_filtered(self._h, nf, ptrs, counts, stride,
+                                                                  P.ctypes.data_as(C.POINTER(C.c_float)), 1 if dev else 0,
+                                                                  C.c_float(leaf), C.byref(n_out)), "setInputTargetFramesFiltered")
+        self._n_target = int(n_out.value)
+        return self._n_target
+
+    def prepareTarget(self):
+        """Builds now, on this object's stream, what the first align against the current target would still have to build (GICP: the
+        target's k-NN covariances; NDT: as a rule nothing) and returns when it is done.  Needs no input source."""
+        capi.check(self._lib.lsr_prepare_target(self._h), "prepareTarget")
+
+    def targetPrepared(self) -> bool:
+        """True when an align with this object's parameters has nothing left to build on the current target (LSR_TARGET_PREPARED)."""
+        return bool(self._geti(capi.TARGET_PREPARED))
 
     def setInputSource(self, cloud):  # scanmatcher_component.cpp:329; graph_based_slam_component.cpp:181
         p, stride, n, dev, keep = _cloud_args(cloud, self)
