@@ -122,7 +122,10 @@ typedef struct lsr_result {
   int32_t converged;            /* hasConverged()                             scanmatcher_component.cpp:375 */
   int32_t iterations;           /* nr_iterations_ */
   double score;                 /* NDT: trans_probability_ (= score / N); GICP: final mean Mahalanobis cost */
-  int32_t n_evaluations;        /* NDT: derivative passes launched; GICP: Gauss-Newton inner steps */
+  int32_t n_evaluations;        /* NDT: derivative evaluations as the reference counts them (computeDerivatives calls + the
+                                   computeHessian after a line search that took trial steps).  The tenth trial of a search
+                                   and the computeHessian behind it are ONE launch here and count as two.
+                                   GICP: Gauss-Newton inner steps */
   int32_t n_correspondences;    /* GICP: pairs in the last outer iteration; NDT: valid (point, voxel) pairs of the last derivative pass */
   double gpu_ms;                /* HOST wall-clock time of the align call that produced this result, from the first
                                    enqueue to the result in host memory; for lsr_align_batch every member carries the
@@ -132,7 +135,8 @@ typedef struct lsr_result {
 typedef struct lsr_profile {
   double deriv_ms_total;        /* hipEvent time of the derivative-launch chains since last reset (events bracket every
                                    chunk of launches as enqueued: launch-to-launch time, dependent-launch gap included) */
-  int64_t deriv_launches;       /* derivative passes that ran in those chains */
+  int64_t deriv_launches;       /* launches of those chains that evaluated points: n_evaluations minus the line searches
+                                   that ran to their tenth trial (for a batch: of the member with the most) */
   int64_t deriv_points;         /* source points processed by those launches */
   int64_t deriv_pairs;          /* valid (point,voxel) pairs of the LAST launch (K-bar * N) */
 } lsr_profile;
@@ -408,9 +412,14 @@ int lsr_ndt_grid_dump(lsr_handle h, int32_t* idx, int32_t* npts, double* mean, d
  * eigen check invalidated (npts = -1) are in the kd-tree and have their centroid. */
 int lsr_ndt_grid_centroids(lsr_handle h, float* centroid);
 /* One derivative pass at pose p = (tx,ty,tz,rx,ry,rz); T16 (nullable, col-major) overrides the point
- * transform like the first pass of align().  grad: 6, hess: 36 (row-major). */
+ * transform like the first pass of align().  grad: 6, hess: 36 (row-major).
+ * compute_hessian: 0 the gradient-only pass of a line-search trial (hess comes back zero), 1 the pass with Hessian,
+ * 2 the fused pass of a search's tenth trial: score and gradient are the bits of form 0, the Hessian the bits of form 1. */
 int lsr_ndt_derivatives(lsr_handle h, const double* p6, const float* T16, int compute_hessian, double* score,
                         double* grad, double* hess);
+/* The same; pairs (nullable) receives the number of valid (point, voxel) pairs of the pass. */
+int lsr_ndt_derivatives_pairs(lsr_handle h, const double* p6, const float* T16, int compute_hessian, double* score,
+                              double* grad, double* hess, double* pairs);
 /* GICP per-point covariances after setInput*: which = 0 source, 1 target (regularised, as the optimiser uses them);
  * 2 source, 3 target: the k-neighbour sample covariance BEFORE the eigen-regularisation.  cov: n*9 doubles. */
 int lsr_gicp_covariances(lsr_handle h, int which, double* cov);

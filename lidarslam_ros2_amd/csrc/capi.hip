@@ -515,7 +515,9 @@ int run_ndt_feeder(lsr_handle h, const NdtProblem* d_probs, const NdtProblem* h_
 }
 
 int ndt_hard_cap(const NdtParamsHost& p) {
-  // per Newton iteration: 1 first pass + <=10 trials + 1 Hessian recomputation; max_iter+2 iterations; + initial pass
+  // per Newton iteration: 1 first pass + <=10 trials + 1 Hessian recomputation; max_iter+2 iterations; + initial pass.
+  // A search that runs to the tenth trial takes its Hessian from that trial's pass (PH_MT_LAST) and needs one launch less, so
+  // this stays an upper bound; the searches that stop after 1-9 trials still reach 1 + 9 + 1.
   return (p.max_iterations + 2) * 12 + 5;
 }
 
@@ -747,7 +749,7 @@ int align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* finals, 
     int passes = 0;
     lead->prof.deriv_pairs = 0;
     for (int b = 0; b < B; b++) {
-      passes = std::max(passes, M[b].n_evals);
+      passes = std::max(passes, M[b].n_passes);   // launches that evaluated points (n_evals counts a fused pass twice)
       lead->prof.deriv_pairs += (int64_t)M[b].last_pairs;
     }
     lead->prof.deriv_ms_total += ev_ms;
@@ -1956,8 +1958,13 @@ int lsr_ndt_grid_centroids(lsr_handle h, float* centroid) {
 
 int lsr_ndt_derivatives(lsr_handle h, const double* p6, const float* T16, int compute_hessian, double* score, double* grad,
                         double* hess) {
+  return lsr_ndt_derivatives_pairs(h, p6, T16, compute_hessian, score, grad, hess, nullptr);
+}
+
+int lsr_ndt_derivatives_pairs(lsr_handle h, const double* p6, const float* T16, int compute_hessian, double* score, double* grad,
+                              double* hess, double* pairs) {
   LSR_CHECK_HANDLE(h);
-  if (!p6) return LSR_ERR_INVALID_ARGUMENT;
+  if (!p6 || compute_hessian < 0 || compute_hessian > 2) return LSR_ERR_INVALID_ARGUMENT;
   if (!h->target || h->target->n == 0) return LSR_ERR_NO_TARGET;
   if (!h->has_source) return LSR_ERR_NO_SOURCE;
   int st = ensure_ndt_grid(h);
@@ -1989,6 +1996,7 @@ int lsr_ndt_derivatives(lsr_handle h, const double* p6, const float* T16, int co
   if (score) *score = S.score;
   if (grad) for (int i = 0; i < 6; i++) grad[i] = S.g[i];
   if (hess) for (int i = 0; i < 36; i++) hess[i] = compute_hessian ? S.H[i] : 0.0;
+  if (pairs) *pairs = S.last_pairs;
   return LSR_OK;
 }
 

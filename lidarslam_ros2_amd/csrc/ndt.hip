@@ -138,7 +138,7 @@ void ndt_fill_diag_state(NdtState& st, const double* p6, const float* T16, int c
     pose_to_T12(p6, st.T);
   }
   angle_tables(p6, true, st.d1_sign, st.jang, st.hang);
-  st.want_hessian = compute_hessian ? 1 : 0;
+  st.want_hessian = compute_hessian == 2 ? NDT_PASS_FUSED : (compute_hessian ? NDT_PASS_HESS : NDT_PASS_GRAD);
   st.phase = PH_DIAG;
 }
 
@@ -471,9 +471,12 @@ __device__ __forceinline__ int ndt_controller_mt(LdsState* S, const LdsDouble* s
   for (int k = 0; k < 8; k++) sv[k] = sums[k];
   const int phase = S->phase;
   const bool had_hessian = S->want_hessian != 0;
-  const int n_evals = S->n_evals + 1;
+  // the last trial of a capped search is two of the reference's evaluations (trial + computeHessian) in one pass
+  const int n_evals = S->n_evals + (phase == PH_MT_LAST ? 2 : 1);
+  const int n_passes = S->n_passes + 1;
   if (phase == PH_INIT || phase == PH_MT_HESS || phase == PH_DIAG) {
     S->n_evals = n_evals;
+    S->n_passes = n_passes;
     S->last_pairs = sv[7];
     if (phase != PH_MT_HESS) {  // the Hessian recomputation leaves score and gradient of the last trial in place
       S->score = sv[0];
@@ -500,7 +503,7 @@ __device__ __forceinline__ int ndt_controller_mt(LdsState* S, const LdsDouble* s
     }
     return phase == PH_INIT ? CTL_NEWTON_BEGIN : CTL_NEWTON_END;
   }
-  // ---- PH_MT_FIRST / PH_MT_TRIAL: one batch of loads
+  // ---- PH_MT_FIRST / PH_MT_TRIAL / PH_MT_LAST: one batch of loads
   int open_interval = S->open_interval, interval_converged = S->interval_converged, step_iterations = S->step_iterations;
   const double step_max = S->step_max, step_min = S->step_min;
   double p[6], dir[6];
@@ -518,7 +521,7 @@ __device__ __forceinline__ int ndt_controller_mt(LdsState* S, const LdsDouble* s
   const double d_phi_t = -dot;
   const double psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t;
   const double d_psi_t = d_phi_t - mu * d_phi_0;
-  if (phase == PH_MT_TRIAL) {
+  if (phase == PH_MT_TRIAL || phase == PH_MT_LAST) {
     if (open_interval && (psi_t <= 0 && d_psi_t >= 0)) {
       open_interval = 0;
       I.f_l = I.f_l + phi_0 - mu * d_phi_0 * I.a_l;
@@ -542,9 +545,14 @@ __device__ __forceinline__ int ndt_controller_mt(LdsState* S, const LdsDouble* s
 #pragma unroll
     for (int i = 0; i < 6; i++) S->x_t[i] = p[i] + dir[i] * a_t;
     S->a_t = a_t;
-    S->want_hessian = 0;
-    S->phase = PH_MT_TRIAL;
-    S->pad1 = 1;  // build T / jang for x_t
+    // Trial number max_step_iterations ends the search whatever it returns: the Hessian the search recomputes at its last x_t
+    // rides along (values 8-28 of the same pass), which saves the PH_MT_HESS launch of every search that runs to the cap.
+    const bool last = step_iterations + 1 >= max_step_iterations;
+    S->want_hessian = last ? NDT_PASS_FUSED : NDT_PASS_GRAD;
+    S->phase = last ? PH_MT_LAST : PH_MT_TRIAL;
+    S->pad1 = 1;  // build T / jang for x_t; hang stays the one of the iteration's first pass, as in PH_MT_HESS below
+  } else if (phase == PH_MT_LAST) {
+    next = CTL_NEWTON_END;  // sums[8..28] of this pass are the recomputed Hessian
   } else if (step_iterations) {
     // computeHessian at x_t: current j_ang, h_ang left over from the last with-Hessian pass; same pose, no new request
     S->want_hessian = 1;
@@ -554,6 +562,7 @@ __device__ __forceinline__ int ndt_controller_mt(LdsState* S, const LdsDouble* s
   }
   // ---- one batch of stores
   S->n_evals = n_evals;
+  S->n_passes = n_passes;
   S->last_pairs = sv[7];
   S->score = score;
 #pragma unroll
@@ -787,6 +796,8 @@ struct Offsets<27> {
 //  * a CHUNK = 64 consecutive source points [64 c, 64 c + 63] (absent points count as zeros): its fp64 total is formed by a
 //    fixed tree — gradient-only passes (8 values): eight runs of 8 consecutive points, each summed left to right in fp64, then a
 //    butterfly over the runs (xor 1, 2, 4); passes with Hessian (29 values): four runs of 16, then a butterfly (xor 1, 2);
+//    the fused pass of a line search's tenth trial (NDT_PASS_FUSED): values 0-7 by the first tree, values 8-28 by the second
+//    — the trial's score and gradient and the recomputed Hessian keep the bits they had as two passes;
 //  * chunk totals are added EXACTLY: each is split into NDT_NBINS signed 31-bit pieces against the fixed binary quanta
 //    q_k = 2^(62 - 31 (k + 1)) (ndt.hpp) and the pieces are summed as integers — associative, so neither the order in which
 //    chunks arrive nor the workgroup that owns a chunk can change a bit.
@@ -1009,6 +1020,7 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
       mb->converged = L->converged;
       mb->nr_iterations = L->nr_iterations;
       mb->n_evals = L->n_evals;
+      mb->n_passes = L->n_passes;
       mb->trans_probability = L->trans_probability;
       mb->last_pairs = L->last_pairs;
       __threadfence_system();
@@ -1024,7 +1036,9 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
   LSR_PASS_MARK(_p_t7)
 
   // ---- this launch's request, straight from the LDS image
-  const bool hess = uniform_i(L->want_hessian) != 0;
+  const int form = uniform_i(L->want_hessian);   // NdtPassForm
+  const bool hess = form != NDT_PASS_GRAD;       // phases A and B form all 29 terms
+  const bool fused = form == NDT_PASS_FUSED;     // phase C: values 0-7 by the gradient tree, 8-28 by the Hessian tree
   const double d1d = uniform_d(L->d1);
   const float d2 = uniform_f((float)L->d2);
   float T[12];
@@ -1038,7 +1052,7 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
 
   // Per batch of PTS points:
   //  A (all 4 PTS lanes, four per point): transform, neighbourhood, pair terms, quad combine;
-  //  B the 29 Jacobian / Hessian terms of the point.  With Hessian: the 14 per-point sums go through LDS to ONE lane per point
+  //  B the 29 Jacobian / Hessian terms of the point.  With Hessian (and fused): the 14 per-point sums go through LDS to ONE lane per point
   //    (two full waves instead of eight quarter-full ones: ~150 instructions per wave); gradient-only passes (three in four)
   //    form their 8 terms right where the sums are, in every lane of the quad — ~30 instructions, no barrier, no LDS round trip;
   //  C: the canonical chunk sums (canon:: above) of the batch's PTS / 64 chunks, straight into the accumulator bank.
@@ -1186,7 +1200,10 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
     // ---- phase C: the float terms of the reference's per-point sums, summed in double chunk by chunk (canon::) and added
     // to the bank piece by piece: the integer pieces of the batch's chunks meet in one lane first (shuffle), so a value
     // costs at most NDT_NBINS atomics per batch
-    if (!hess) {
+    // A fused pass (the last trial of a capped line search) reduces values 0-7 exactly as a gradient-only pass does and values
+    // 8-28 exactly as a pass with Hessian does — on different waves, so neither tree waits for the other: the first PTS lanes
+    // take the gradient tree, the whole waves behind them the Hessian tree.
+    if (!hess || fused) {
       constexpr int RUNS = PTS / 8;                       // runs of 8 points per value: 8 per chunk
       if (tid < NDT_NRED_GRAD * RUNS) {                   // whole waves
         const int v = tid / RUNS, k = tid & 7;
@@ -1201,10 +1218,15 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
           if (pz && k == 0) atomicAdd(dst + 31, 1ull);
         }
       }
-    } else {
+    }
+    if (hess) {
       constexpr int RUNS = PTS / 16;                      // runs of 16 points per value: 4 per chunk
-      if (tid < ((29 * RUNS + 63) & ~63)) {               // whole waves, the lanes beyond value 28 idle along
-        const int v = tid / RUNS, sg = tid & 3;
+      static_assert(NDT_NRED_GRAD * (PTS / 8) % 64 == 0 && NDT_NRED_GRAD * (PTS / 8) + (((29 - NDT_NRED_GRAD) * RUNS + 63) & ~63) <= THREADS,
+                    "fused pass: the two trees sit on whole waves of their own");
+      const int v0 = fused ? NDT_NRED_GRAD : 0;           // first value of the Hessian tree
+      const int ht = tid - (fused ? NDT_NRED_GRAD * (PTS / 8) : 0);   // lane of the Hessian tree (a multiple of 64 away from tid)
+      if (ht >= 0 && ht < (((29 - v0) * RUNS + 63) & ~63)) {   // whole waves, the lanes beyond value 28 idle along
+        const int v = v0 + ht / RUNS, sg = tid & 3;
         double t = 0.0;
         if (v < 29) t = canon::reduce_hess(&s_o[v][16 * (tid % RUNS)]);
         bool poison, poison0;
@@ -1373,6 +1395,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
       mb->converged = L->converged;
       mb->nr_iterations = L->nr_iterations;
       mb->n_evals = L->n_evals;
+      mb->n_passes = L->n_passes;
       mb->trans_probability = L->trans_probability;
       mb->last_pairs = L->last_pairs;
       __threadfence_system();
@@ -1386,7 +1409,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
   }
 
   // ---- this launch's request: wave-uniform values in scalar registers
-  const bool hess = uniform_i(L->want_hessian) != 0;
+  const int form = uniform_i(L->want_hessian);   // NdtPassForm
+  const bool hess = form != NDT_PASS_GRAD;       // all 29 terms of a point
+  const bool fused = form == NDT_PASS_FUSED;     // values 0-7 by the gradient tree, 8-28 by the Hessian tree
   const double d1d = uniform_d(L->d1);
   const float d2 = uniform_f((float)L->d2);
   float T[12];
@@ -1579,9 +1604,14 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         for (int k = 0; k < 16; k++)
           if (16 * r + k < 29) s_tile[k * canon::TILE_PITCH + lane] = o[16 * r + k];
         wave_lds_fence();
+        if (fused && r == 0) {   // rows 0-7 of the first tile: the sums of a gradient-only pass, bit for bit
+          const int vg = lane >> 3, g = lane & 7;
+          const double tg = canon::reduce_grad(s_tile + vg * canon::TILE_PITCH + 8 * g);
+          if (g < NDT_NBINS) canon::add_piece_lds(s_ibin, vg, g, tg);
+        }
         const int v = 16 * r + (lane >> 2), sg = lane & 3;
         const double t = canon::reduce_hess(s_tile + (lane >> 2) * canon::TILE_PITCH + 16 * sg);
-        if (v < 29) {
+        if (v < 29 && !(fused && v < NDT_NRED_GRAD)) {
           canon::add_piece_lds(s_ibin, v, sg + 1, t);          // lanes 0..3 of the value take bins 1..4,
           if (sg == 0) canon::add_piece_lds(s_ibin, v, 0, t);   // lane 0 also bin 0 (zero unless the total exceeds 2^31)
         }

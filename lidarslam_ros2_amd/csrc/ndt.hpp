@@ -17,7 +17,16 @@ enum NdtPhase : int {
   PH_MT_FIRST = 1,  // first pass of a line search (with Hessian)
   PH_MT_TRIAL = 2,  // More-Thuente trial (gradient only)
   PH_MT_HESS = 3,   // Hessian recomputation after trials
-  PH_DIAG = 4       // lsr_ndt_derivatives: store sums and stop
+  PH_DIAG = 4,      // lsr_ndt_derivatives: store sums and stop
+  PH_MT_LAST = 5    // the trial that ends the search whatever it returns (number max_step_iterations): gradient AND Hessian in one pass
+};
+
+// NdtState::want_hessian, the form of the pass a request asks for
+enum NdtPassForm : int {
+  NDT_PASS_GRAD = 0,   // 8 values, gradient tree (canon::reduce_grad)
+  NDT_PASS_HESS = 1,   // 29 values, Hessian tree (canon::reduce_hess)
+  NDT_PASS_FUSED = 2   // 29 values: 0-7 by the gradient tree, 8-28 by the Hessian tree = the bits of a gradient-only pass and of
+                       // the Hessian recomputation that would follow it at the same pose
 };
 
 constexpr int NDT_NRED = 32;       // doubles per partial row: [0]=score [1..6]=grad [7]=#pairs [8..28]=Hessian upper triangle
@@ -80,8 +89,11 @@ struct NdtState {
   float final_T[16];  // column-major 4x4
   double trans_probability;
   double last_pairs;
-  int n_evals, pad1;
+  int n_evals, pad1;   // n_evals: derivative evaluations as the reference counts them (a fused pass counts as two)
+  int n_passes;        // passes that evaluated points = launches the controller has consumed
+  int pad2[3];         // the state is copied as uint4
 };
+static_assert(sizeof(NdtState) % 16 == 0 && sizeof(NdtState) <= 128 * 16, "NdtState travels as at most 128 uint4");
 
 // Host mailbox of a single registration (pinned, host-coherent memory mapped into the device): the chain reports its
 // progress and its result straight into host memory, so the host feeds launches and detects the end of an align()
@@ -92,6 +104,7 @@ struct NdtMailbox {
   int converged, nr_iterations, n_evals;
   double trans_probability, last_pairs;
   float final_T[16];            // column-major 4x4
+  int n_passes;                 // NdtState::n_passes at the end
 };
 
 // One registration problem as the kernels see it (array of these for batched launches).

@@ -433,16 +433,21 @@ class NormalDistributionsTransform(Registration):
         capi.check(self._lib.lsr_ndt_grid_centroids(self._h, c.ctypes.data_as(C.POINTER(C.c_float))), "gridCentroids")
         return c
 
-    def derivatives(self, p, T=None, compute_hessian: bool = True):
+    def derivatives(self, p, T=None, compute_hessian=True, with_pairs: bool = False):
+        """One derivative pass.  compute_hessian: False / True, or 2 for the fused form of a line search's tenth trial (score and
+        gradient reduced as a gradient-only pass, the Hessian as a pass with Hessian).  with_pairs: also return the pair count."""
         p = np.ascontiguousarray(p, np.float64)
         t = _mat_to_col16(T) if T is not None else None
-        score = C.c_double()
+        score, pairs = C.c_double(), C.c_double()
         g, H = np.zeros(6), np.zeros((6, 6))
-        capi.check(self._lib.lsr_ndt_derivatives(self._h, p.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 t.ctypes.data_as(C.POINTER(C.c_float)) if t is not None else None,
-                                                 1 if compute_hessian else 0, C.byref(score),
-                                                 g.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 H.ctypes.data_as(C.POINTER(C.c_double))), "derivatives")
+        form = 2 if (compute_hessian is not True and compute_hessian == 2) else (1 if compute_hessian else 0)
+        capi.check(self._lib.lsr_ndt_derivatives_pairs(self._h, p.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       t.ctypes.data_as(C.POINTER(C.c_float)) if t is not None else None,
+                                                       form, C.byref(score),
+                                                       g.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       H.ctypes.data_as(C.POINTER(C.c_double)), C.byref(pairs)), "derivatives")
+        if with_pairs:
+            return score.value, g, H, pairs.value
         return score.value, g, H
 
 
