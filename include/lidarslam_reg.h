@@ -423,6 +423,20 @@ int lsr_ndt_derivatives_pairs(lsr_handle h, const double* p6, const float* T16, 
 /* GICP per-point covariances after setInput*: which = 0 source, 1 target (regularised, as the optimiser uses them);
  * 2 source, 3 target: the k-neighbour sample covariance BEFORE the eigen-regularisation.  cov: n*9 doubles. */
 int lsr_gicp_covariances(lsr_handle h, int which, double* cov);
+/* GICP, one linearisation as lsr_align(h, guess16) runs it: the first correspondence pass and the first Gauss-Newton accumulation
+ * of an outer iteration whose transformation_ is trans16 (col-major; NULL = identity, the first outer iteration), by the launches
+ * of lsr_align itself (LSR_GICP_FUSED / LSR_GICP_CORR_FUSED / LSR_GICP_BALL / LSR_NN_COOP pick the form); nothing else of the outer
+ * iteration runs, and a later lsr_align returns what it would have returned without the call.  Inspection only (parity tests).
+ * use_seeds != 0: the neighbours the previous lsr_align / lsr_gicp_linearize on this source and target left behind are offered as
+ * search seeds, as from the second outer iteration on (LSR_ERR_INVALID_ARGUMENT when there are none).
+ * Outputs, each nullable: out[n*3] = guess * source; nn_idx[n] neighbour in the target (-1: none within the gate);
+ * valid[n]; M6[n*6] = (C2_j + R C1_i R^T)^-1 as 00 01 02 11 12 22 (zero where valid = 0); q[n*3] the paired target point;
+ * x6 / T12 (row-major 3x4, fp32) / dR27 (dR/dphi, dR/dtheta, dR/dpsi, row-major) of the state the accumulation ran at;
+ * m = the pair count the chain adopted; sums28 = the reduced sums before the division by m: [0] sum r^T M r, [1..6] J^T M r,
+ * [7..27] the upper triangle of J^T M J row by row.  m < 4 returns LSR_OK and m; sums28 then carries no meaning.
+ * LSR_ERR_TOO_FEW_POINTS as lsr_align. */
+int lsr_gicp_linearize(lsr_handle h, const float* guess16, const float* trans16, int use_seeds, float* out, int32_t* nn_idx,
+                       int32_t* valid, double* M6, float* q, double* x6, float* T12, double* dR27, int32_t* m, double* sums28);
 /* 1-NN of the source transformed by T16 (nullable = identity) in the target: idx[n], d2[n]. */
 int lsr_nearest_neighbors(lsr_handle h, const float* T16, int32_t* idx, float* d2);
 int lsr_get_profile(lsr_handle h, lsr_profile* out, int reset);

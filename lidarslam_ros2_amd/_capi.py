@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "lsr_debug_angle_tables", "lsr_set_input_source_pc2", "lsr_get_source_pc2", "lsr_voxel_grid_filter_pc2", "lsr_shard_range", "lsr_comm_unique_id", "lsr_comm_create", "lsr_comm_destroy", "lsr_align_batch_sharded",
     "lsr_shard_plan", "lsr_align_batch_planned", "lsr_align_fitness_batch",
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
-    "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target",
+    "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
 ]
 
 
@@ -137,6 +137,7 @@ def load() -> C.CDLL:
     L.lsr_ndt_derivatives_pairs.argtypes = [vp, dp, fp, C.c_int, dp, dp, dp, dp]
     L.lsr_gicp_covariances.argtypes = [vp, C.c_int, dp]
     L.lsr_nearest_neighbors.argtypes = [vp, fp, ip, fp]
+    L.lsr_gicp_linearize.argtypes = [vp, fp, fp, C.c_int, fp, ip, ip, dp, fp, dp, fp, dp, ip, dp]
     L.lsr_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
     L.lsr_debug_angle_tables.argtypes = [dp, C.c_int, fp, fp, fp, fp]
     L.lsr_set_input_source_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_double, C.c_float, C.c_int,

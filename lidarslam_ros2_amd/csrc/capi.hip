@@ -2006,6 +2006,14 @@ int lsr_gicp_covariances(lsr_handle h, int which, double* cov) {
   return gicp_get_covariances(h, which, cov);
 }
 
+int lsr_gicp_linearize(lsr_handle h, const float* guess16, const float* trans16, int use_seeds, float* out, int32_t* nn_idx,
+                       int32_t* valid, double* M6, float* q, double* x6, float* T12, double* dR27, int32_t* m, double* sums28) {
+  LSR_CHECK_HANDLE(h);
+  if (h->method != LSR_METHOD_GICP) { set_last_error("lsr_gicp_linearize on an NDT object"); return LSR_ERR_INVALID_ARGUMENT; }
+  const GicpLinearizeOut o{out, nn_idx, valid, M6, q, x6, T12, dR27, m, sums28};
+  return gicp_linearize(h, guess16, trans16, use_seeds, o);
+}
+
 int lsr_get_profile(lsr_handle h, lsr_profile* out, int reset) {
   LSR_CHECK_HANDLE(h);
   if (out) *out = h->prof;

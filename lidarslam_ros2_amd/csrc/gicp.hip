@@ -842,7 +842,8 @@ __host__ __device__ inline void gicp_begin_outer(IterBlock& B) {
 }
 
 __global__ __launch_bounds__(256) void gicp_update_kernel(IterBlock* __restrict__ B, const double* __restrict__ partials, int nblocks,
-                                                          GicpMailbox* mb, unsigned int token, int launch_index) {
+                                                          GicpMailbox* mb, unsigned int token, int launch_index,
+                                                          double* __restrict__ sums_out /* nullable: inspection */) {
   GnState* S = &B->st;
   OuterState* O = &B->out;
   const unsigned long long progress = ((unsigned long long)token << 32) | (unsigned int)launch_index;
@@ -868,6 +869,7 @@ __global__ __launch_bounds__(256) void gicp_update_kernel(IterBlock* __restrict_
     s_sum[t] = v;
   }
   __syncthreads();
+  if (sums_out && t < GN_NRED) sums_out[t] = s_sum[t];   // lsr_gicp_linearize: the reduced sums as the step below reads them
   if (t != 0) return;
   bool finished = false;
   if (!(ph & 1)) {  // first step of this outer iteration: the correspondence pass has just run, adopt its pair count
@@ -1055,7 +1057,8 @@ __global__ __launch_bounds__(GN_THREADS) void gicp_step_kernel(IterBlock* __rest
                                                                const float* __restrict__ oy, const float* __restrict__ oz, int n,
                                                                const PairRec* __restrict__ pairs, double* __restrict__ partials2,
                                                                int nblocks, GicpMailbox* mb, unsigned int token, int launch_index,
-                                                               const int* __restrict__ count_shards /* nullable */) {
+                                                               const int* __restrict__ count_shards /* nullable */,
+                                                               double* __restrict__ sums_out /* nullable: inspection */) {
   static_assert(sizeof(IterBlock) % 8 == 0, "IterBlock is copied as 8-byte words");
   __shared__ __attribute__((aligned(16))) unsigned long long s_raw[sizeof(IterBlock) / 8];
   __shared__ double s_grp[8][32];
@@ -1093,6 +1096,8 @@ __global__ __launch_bounds__(GN_THREADS) void gicp_step_kernel(IterBlock* __rest
       double v2 = 0.0;
       for (int g2 = 0; g2 < 8; g2++) v2 += s_grp[g2][t];
       s_sum[t] = v2;
+      // lsr_gicp_linearize: the reduced sums as gicp_advance / solve6_gn_wave read them below
+      if (sums_out && blockIdx.x == 0 && t < GN_NRED) sums_out[t] = v2;
     }
   }
   __syncthreads();
@@ -1340,6 +1345,7 @@ struct GicpChain {
   int* d_work = nullptr;
   int* d_shards = nullptr;
   double* d_partials = nullptr;
+  double* d_sums = nullptr;   // lsr_gicp_linearize only: where the consuming step leaves the reduced sums
   IterBlock* d_blk = nullptr;
   PairRec* d_pairs = nullptr;
   long hard_cap = 0;
@@ -1375,7 +1381,8 @@ struct GicpChain {
       }
       for (int it = 0; it < steps; it++) {
         hipLaunchKernelGGL(gicp_step_kernel, dim3(nblocks), dim3(GN_THREADS), 0, s, d_blk, updates, ws.out.x(), ws.out.y(), ws.out.z(), n,
-                           d_pairs, d_partials, nblocks, ws.d_mailbox, token, updates + 1, corr_fused ? (const int*)d_shards : (const int*)nullptr);
+                           d_pairs, d_partials, nblocks, ws.d_mailbox, token, updates + 1, corr_fused ? (const int*)d_shards : (const int*)nullptr,
+                           d_sums);
         updates++;
       }
       return;
@@ -1394,12 +1401,15 @@ struct GicpChain {
       hipLaunchKernelGGL(gicp_gn_kernel, dim3(nblocks), dim3(GN_THREADS), 0, s, ws.out.x(), ws.out.y(), ws.out.z(), n, d_pairs,
                          &d_blk->st, &d_blk->out, d_partials);
       updates++;
-      hipLaunchKernelGGL(gicp_update_kernel, dim3(1), dim3(256), 0, s, d_blk, d_partials, nblocks, ws.d_mailbox, token, updates);
+      hipLaunchKernelGGL(gicp_update_kernel, dim3(1), dim3(256), 0, s, d_blk, d_partials, nblocks, ws.d_mailbox, token, updates, d_sums);
     }
   }
 
-  // everything up to the first three groups of launches
-  int begin(lsr_handle_s* handle, const float* guess) {
+  // everything up to the first three groups of launches.
+  // lin (lsr_gicp_linearize): the same start with transformation_ = lin->trans, then ONE correspondence pass and the accumulation at
+  // the start x of that outer iteration, consumed by a step that cannot move x (max_inner = 0) and ends the align (max_iterations = 1).
+  struct Linearize { const float* trans; bool use_seeds; };
+  int begin(lsr_handle_s* handle, const float* guess, const Linearize* lin = nullptr) {
     h = handle;
     if (!h->target || h->target->n == 0) { set_last_error("align before setInputTarget"); return LSR_ERR_NO_TARGET; }
     if (!h->has_source) { set_last_error("align before setInputSource"); return LSR_ERR_NO_SOURCE; }
@@ -1413,12 +1423,18 @@ struct GicpChain {
     // workspace: out cloud | pairs | partials | per-align block {inner state, T16, Rm, outer state, count} | guess
     nblocks = std::max(1, std::min((n + GN_THREADS - 1) / GN_THREADS, 512));
     GicpWorkspace& ws = h->gicp_ws;
+    const bool seeds = lin && lin->use_seeds;
+    if (seeds && (ws.seed_n != n || ws.seed_tn != (long)h->target->n)) {
+      set_last_error("use_seeds: no earlier pass on this source and target left neighbours behind");
+      return LSR_ERR_INVALID_ARGUMENT;
+    }
     if ((st = ws.out.resize(n))) return st;
     if ((st = ws.pairs.reserve((size_t)n * sizeof(PairRec)))) return st;
     if ((st = ws.buf.reserve((size_t)2 * nblocks * 32 + 64))) return st;   // two banks of partial rows (fused chain)
     if ((st = ws.state.reserve(2 * sizeof(IterBlock) + 256))) return st;   // the block is double buffered by step parity
     if ((st = ws.pin.reserve(sizeof(IterBlock) + 64))) return st;
     d_partials = ws.buf.p;
+    d_sums = lin ? ws.buf.p + (size_t)2 * nblocks * 32 : nullptr;   // the 64 doubles behind the two banks
     d_blk = reinterpret_cast<IterBlock*>(ws.state.p);
     d_pairs = reinterpret_cast<PairRec*>(ws.pairs.p);
 
@@ -1444,6 +1460,12 @@ struct GicpChain {
     O.corr_mark = -1;
     O.token = token;
     hb->st.max_inner = h->gicp.max_inner;
+    if (lin) {
+      if (lin->trans) std::memcpy(O.trans, lin->trans, sizeof(I16));
+      O.max_iterations = 1;
+      hb->st.max_inner = 0;
+      O.phase = seeds ? 2 : 0;   // an outer iteration after the first: last_nn is offered as seeds
+    }
     gicp_begin_outer(*hb);
     thr2 = (float)(h->gicp.max_corr_dist * h->gicp.max_corr_dist);
 
@@ -1470,6 +1492,13 @@ struct GicpChain {
       if ((st = ws.count_shards.reserve((size_t)GICP_COUNT_SHARDS * GICP_SHARD_STRIDE))) return st;
       d_shards = ws.count_shards.p;
       zero_words = d_shards; n_zero = GICP_COUNT_SHARDS * GICP_SHARD_STRIDE;
+      if (seeds && ws.lin_total >= 0) {   // as between two outer iterations: the counters run on, the block remembers their total
+        n_zero = 0;
+        hb->count_base = (int)ws.lin_total;
+      } else if (lin) {
+        ws.lin_total = 0;
+      }
+      if (!lin) ws.lin_total = -1;        // an align leaves the counters at a total nobody reads back
     } else if (ball) {
       if ((st = ws.corr_work.reserve((size_t)n + 2))) return st;
       d_work = ws.corr_work.p;
@@ -1478,6 +1507,14 @@ struct GicpChain {
     // iteration block + zeroed counters + guess-moved source: one launch (gicp_begin_align_kernel)
     hipLaunchKernelGGL(gicp_begin_align_kernel, dim3((n + 255) / 256), dim3(256), 0, s, h->source.x(), h->source.y(), h->source.z(), n, *hb, d_blk,
                        zero_words, n_zero, ws.out.x(), ws.out.y(), ws.out.z());
+    ws.seed_n = n;   // the first correspondence pass writes every entry of last_nn
+    ws.seed_tn = (long)h->target->n;
+    if (lin) {   // one pass, one accumulation, the step that consumes it
+      LSR_HIP(hipMemsetAsync(d_sums, 0, sizeof(double) * 32, s));
+      enqueue_group(fused ? 2 : 1);
+      LSR_HIP(hipGetLastError());
+      return LSR_OK;
+    }
     // the first outer iteration typically needs 3-4 Gauss-Newton steps, later ones one or two; the fused chain needs one step
     // more per outer iteration (the step that finds the loop finished accumulates nothing)
     enqueue_group(fused ? 5 : 4);
@@ -1549,6 +1586,46 @@ int gicp_align(lsr_handle_s* h, const float* guess, float* final_T, lsr_result* 
     if (!c.done) wait_between_polls(h->scratch.wait_mode);
   }
   c.finish(final_T, res);
+  return LSR_OK;
+}
+
+// lsr_gicp_linearize: the first correspondence pass and the first Gauss-Newton accumulation of an outer iteration whose
+// transformation_ is `trans`, by the launches of gicp_align (GicpChain::begin), read back from where they leave their results.
+int gicp_linearize(lsr_handle_s* h, const float* guess, const float* trans, int use_seeds, const GicpLinearizeOut& o) {
+  GicpChain c;
+  const GicpChain::Linearize lin{trans, use_seeds != 0};
+  int st = c.begin(h, guess, &lin);
+  if (st) return st;
+  GicpWorkspace& ws = h->gicp_ws;
+  const size_t n = (size_t)c.n;
+  std::vector<PairRec> pairs(n);
+  std::vector<float> xyz(3 * n);
+  std::vector<int> nn(n);
+  IterBlock blk;
+  double sums[32];
+  const IterBlock* d_final = c.d_blk + (c.fused ? (c.updates & 1) : 0);   // step s leaves the block in bank (s + 1) & 1
+  LSR_HIP(hipMemcpyAsync(&blk, d_final, sizeof(IterBlock), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipMemcpyAsync(sums, c.d_sums, sizeof(sums), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipMemcpyAsync(pairs.data(), c.d_pairs, n * sizeof(PairRec), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipMemcpyAsync(nn.data(), ws.last_nn.p, n * sizeof(int), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipMemcpyAsync(xyz.data(), ws.out.x(), n * sizeof(float), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipMemcpyAsync(xyz.data() + n, ws.out.y(), n * sizeof(float), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipMemcpyAsync(xyz.data() + 2 * n, ws.out.z(), n * sizeof(float), hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipStreamSynchronize(c.s));
+  if (!blk.out.outer_done) { set_last_error("GICP linearize: the launch chain did not reach its end"); return LSR_ERR_HIP; }
+  if (c.corr_fused) ws.lin_total += blk.st.m;
+  for (size_t i = 0; i < n; i++) {
+    if (o.out) { o.out[3 * i] = xyz[i]; o.out[3 * i + 1] = xyz[n + i]; o.out[3 * i + 2] = xyz[2 * n + i]; }
+    if (o.nn_idx) o.nn_idx[i] = nn[i];
+    if (o.valid) o.valid[i] = pairs[i].valid;
+    if (o.M6) for (int k = 0; k < 6; k++) o.M6[6 * i + k] = pairs[i].M[k];
+    if (o.q) for (int k = 0; k < 3; k++) o.q[3 * i + k] = pairs[i].q[k];
+  }
+  if (o.x6) for (int k = 0; k < 6; k++) o.x6[k] = blk.st.x[k];
+  if (o.T12) for (int k = 0; k < 12; k++) o.T12[k] = blk.st.T[k];
+  if (o.dR27) for (int k = 0; k < 27; k++) o.dR27[k] = blk.st.dR[k];
+  if (o.m) *o.m = blk.st.m;
+  if (o.sums28) for (int k = 0; k < GN_NRED; k++) o.sums28[k] = sums[k];
   return LSR_OK;
 }
 

@@ -43,12 +43,21 @@ struct GicpWorkspace {
   PinBuf<GicpMailbox> mailbox;
   GicpMailbox* d_mailbox = nullptr;
   unsigned int token = 0;        // one per align
+  int seed_n = -1;               // last_nn holds a neighbour (or -1) for every point of a source of this size ...
+  long seed_tn = -1;             // ... in a target of this size (lsr_gicp_linearize use_seeds)
+  long lin_total = -1;           // lsr_gicp_linearize: what the pair counters add up to; -1 = unknown (an align ran)
+};
+
+// lsr_gicp_linearize's outputs (include/lidarslam_reg.h), each nullable
+struct GicpLinearizeOut {
+  float* out; int* nn_idx; int* valid; double* M6; float* q; double* x6; float* T12; double* dR27; int* m; double* sums28;
 };
 
 int gicp_align(lsr_handle_s* h, const float* guess, float* final_T, lsr_result* res);
 // B registrations side by side (each chain on its own object's stream, one host loop feeding them all)
 int gicp_align_batch(lsr_handle_s* const* hs, int B, const float* guesses, float* finals, lsr_result* results);
 int gicp_get_covariances(lsr_handle_s* h, int which, double* cov);
+int gicp_linearize(lsr_handle_s* h, const float* guess, const float* trans, int use_seeds, const GicpLinearizeOut& out);
 // lsr_prepare_target: neighbour grid + k-NN covariances of the current target on h's stream, complete on return (no source needed)
 int gicp_prepare_target(lsr_handle_s* h);
 // nothing of the current target is left for an align with h's k_correspondences / gicp_epsilon to build

@@ -477,6 +477,28 @@ class GeneralizedIterativeClosestPoint(Registration):
         super().setInputTarget(cloud)
         self._n_target = int(np.shape(cloud)[0]) if not _is_torch_cuda(cloud) else int(cloud.shape[0])
 
+    def linearize(self, guess=None, trans=None, use_seeds: bool = False) -> dict:
+        """Inspection (lsr_gicp_linearize): the first correspondence pass and the first Gauss-Newton accumulation of the outer
+        iteration of align(guess) whose transformation_ is `trans` (4x4, None = identity), run by align's own launches.
+        use_seeds: offer the neighbours of the previous align / linearize as search seeds (an outer iteration after the first).
+        Returns out (n,3) = guess * source, nn_idx (n,), valid (n,), M6 (n,6) = 00 01 02 11 12 22 of the Mahalanobis matrices,
+        q (n,3) paired target points, x6, T12 (3,4) fp32, dR (3,3,3) of the state, m, sums28 (before the division by m)."""
+        n = self._n_source
+        fp, dp, ip = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        g = _mat_to_col16(guess) if guess is not None else None
+        t = _mat_to_col16(trans) if trans is not None else None
+        r = dict(out=np.zeros((n, 3), np.float32), nn_idx=np.zeros(n, np.int32), valid=np.zeros(n, np.int32),
+                 M6=np.zeros((n, 6)), q=np.zeros((n, 3), np.float32), x6=np.zeros(6), T12=np.zeros((3, 4), np.float32),
+                 dR=np.zeros((3, 3, 3)), sums28=np.zeros(28))
+        m = C.c_int32()
+        capi.check(self._lib.lsr_gicp_linearize(
+            self._h, g.ctypes.data_as(fp) if g is not None else None, t.ctypes.data_as(fp) if t is not None else None,
+            1 if use_seeds else 0, r["out"].ctypes.data_as(fp), r["nn_idx"].ctypes.data_as(ip), r["valid"].ctypes.data_as(ip),
+            r["M6"].ctypes.data_as(dp), r["q"].ctypes.data_as(fp), r["x6"].ctypes.data_as(dp), r["T12"].ctypes.data_as(fp),
+            r["dR"].ctypes.data_as(dp), C.byref(m), r["sums28"].ctypes.data_as(dp)), "linearize")
+        r["m"] = int(m.value)
+        return r
+
 
 def set_input_target_batch(regs: Sequence[Registration], clouds):
     """setInputTarget of every candidate of a set with the builds overlapped on the device (lsr_set_input_target_batch;

@@ -216,6 +216,20 @@ src2 = np.vstack([c.source[:500], c.source[:8] + np.float32([60.0, -45.0, 9.0])]
 g.setInputSource(src2)
 g.align(c.guess)
 out["fit_outliers"] = float(g.getFitnessScore()).hex()
+# one correspondence pass + one Gauss-Newton accumulation at a pose with every angle non-zero, a gate that pairs a part of the scan
+sys.path.insert(0, "tests")
+from gicp_numpy import state
+x = (0.3, -0.2, 0.1, 0.05, -0.08, 0.12)
+P = np.eye(4, dtype=np.float32)
+P[:3, :3] = state(x)[0].astype(np.float32)
+P[:3, 3] = np.float32(x[:3])
+g.setInputSource(c.source[:1501])
+g.setMaxCorrespondenceDistance(1.1)
+r = g.linearize(c.guess, P)
+assert 0.2 * 1501 <= r["m"] <= 0.8 * 1501, r["m"]
+# (a neighbour is proven only within the gate: what an unpaired point is left with, -1 or a point beyond the gate, is the search's business)
+r["nn_idx"] = np.where(r["valid"] != 0, r["nn_idx"], -1).astype(np.int32)
+out["lin"] = {k: np.ascontiguousarray(r[k]).tobytes().hex() for k in ("nn_idx", "valid", "M6", "sums28")}
 print("VARIANT " + json.dumps(out))
 """
 
