@@ -260,6 +260,47 @@ int lsr_voxel_grid_filter_pc2(lsr_handle h, const void* data, size_t n_points, c
  * 443-447; graph_based_slam_component.cpp:224-226).  Writes xyz at offset 0 of each out_stride_bytes record. */
 int lsr_voxel_grid_filter(lsr_handle h, const void* pts, size_t stride_bytes, size_t n, float leaf, void* out_pts,
                           size_t out_stride_bytes, size_t out_capacity, size_t* n_out);
+/* ---- IMU de-skew of the raw scan (use_imu: scanmatcher_component.cpp:204-208, 501-527) ------------
+ * The reference's LidarUndistortion (scanmatcher/include/scanmatcher/lidar_undistortion.hpp) keeps a ring of 200 IMU samples and, per
+ * scan, moves every point of the RAW cloud into the sensor frame of the scan's first point before the range filter sees it.  The
+ * ring lives in the handle, on the host; the scan is de-skewed on the device, records in, records out, so that the existing
+ * lsr_set_input_source_pc2 (and the map side) consume the result unchanged.  Two definitions the reference leaves open: a fresh ring
+ * is all zeros, and a sample older than the previous one is refused. */
+/* lidar_undistortion_.setScanPeriod / a fresh LidarUndistortion (lidar_undistortion.hpp:229-237): empties the ring; scan_period > 0 */
+int lsr_imu_reset(lsr_handle h, double scan_period);
+/* lidar_undistortion_.getImu(angular_velo, acc, quat, imu_time)   scanmatcher_component.cpp:525 (lidar_undistortion.hpp:53-106).
+ * ang_vel3 / acc3: 3 floats each, acc3 with gravity already removed (:509-511); quat_wxyz4: w x y z.  A stamp smaller than the
+ * previous sample's: LSR_ERR_INVALID_ARGUMENT, nothing stored.  Needs no device. */
+int lsr_imu_push(lsr_handle h, const float* ang_vel3, const float* acc3, const float* quat_wxyz4, double stamp);
+/* ScanMatcherComponent::receiveImu(msg)   scanmatcher_component.cpp:501-527: the same from the fields of a sensor_msgs/Imu message —
+ * orientation x y z w, angular velocity, linear acceleration, all double.  Removes gravity from the acceleration with the roll / pitch
+ * of the orientation (:505-511) and pushes the sample (lsr_imu_push; same refusal).  The only implementation of that arithmetic: the
+ * C++ classes and the Python binding call this entry.  Needs no device. */
+int lsr_imu_receive(lsr_handle h, const double* orientation_xyzw4, const double* angular_velocity3, const double* linear_acceleration3,
+                    double stamp);
+/* inspection: info4 = {samples accepted since the reset, imu_ptr_last_, imu_ptr_last_iter_, 0} */
+int lsr_imu_info(lsr_handle h, int32_t* info4);
+typedef struct lsr_deskew_info {
+  int32_t n_skipped;      /* points left untouched: no IMU sample within scan_period of their time */
+  int32_t start_missing;  /* 1 = the scan's first point is one of them: the whole scan is returned unchanged (the reference reads
+                             uninitialised values there); the IMU pointer still advances */
+  int32_t half_index;     /* first point whose azimuth has passed start + pi (n_points when none does); -1 when nothing ran */
+  int32_t cursor;         /* imu_ptr_last_iter_ after the call */
+} lsr_deskew_info;
+/* lidar_undistortion_.adjustDistortion(tmp_ptr, scan_time)   scanmatcher_component.cpp:207 (lidar_undistortion.hpp:110-226).
+ * data: n_points records of layout->point_step bytes in payload order (the order is the scan's time axis); out_data: the same
+ * records with x / y / z moved and every other byte copied.  on_device != 0: both are HIP device pointers (ordering rules as for every
+ * device input above), equal (in place) or disjoint (ranges that overlap otherwise: LSR_ERR_INVALID_ARGUMENT); the call returns when the
+ * records are complete, for a reader on any stream, and performs no device-to-host copy and no stream synchronisation — except
+ * when the ring is too short and out_data != data: that plain copy is followed by a synchronisation of the handle's stream.  on_device == 0: both are host pointers, equal or disjoint.  With fewer than two samples in
+ * the ring (imu_ptr_last_ <= 0) or n_points == 0 the records are copied unchanged, as the reference leaves them.  info: nullable. */
+int lsr_deskew_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, double scan_time, int on_device,
+                   void* out_data, lsr_deskew_info* info);
+/* inspection, in the style of lsr_ndt_grid_dump: what the last lsr_deskew_pc2 on this handle decided per point (each nullable, n_points
+ * entries): rel_time (lidar_undistortion.hpp:153), the ring slot imu_ptr_front_ stood on (:157-162), skipped (:164-166).  Writes
+ * nothing when that call moved nothing because the ring was too short. */
+int lsr_deskew_trace(lsr_handle h, float* rel_time, int32_t* slot, uint8_t* skipped);
+
 /* Let `h` register against the target already resident in `owner` (N keyframes vs ONE submap):
  * no copy, the voxel grid / target structures are reference counted. */
 int lsr_share_target(lsr_handle h, lsr_handle owner);

@@ -84,6 +84,19 @@ class Gfx950Registration : public pcl::Registration<PointSource, PointTarget> {
     return v;
   }
   lsr_handle handle() const { return h_; }      // for the entry points that have no pcl::Registration counterpart (§3b-3d)
+  // ---- use_imu (scanmatcher_component.cpp:78-80, 204-208, 501-527): the node's LidarUndistortion member, on the device ----
+  void imuReset(double scan_period = 0.1) { report(lsr_imu_reset(h_, scan_period)); }                 // setScanPeriod (:80)
+  // receiveImu (:501-527) from the message's fields (orientation x y z w): the library removes gravity (:505-511), then getImu (:525)
+  bool receiveImu(const double orientation_xyzw[4], const double angular_velocity[3], const double linear_acceleration[3], double stamp) {
+    return lsr_imu_receive(h_, orientation_xyzw, angular_velocity, linear_acceleration, stamp) == LSR_OK;   // false: refused (out of order)
+  }
+  // adjustDistortion (:207) on the raw PointCloud2 payload, records in, records out (host or device pointers, equal or disjoint)
+  bool deskewPointCloud2(const void* data, std::size_t n_points, const lsr_pc2_layout& layout, double scan_time, void* out_data,
+                         bool on_device = false, lsr_deskew_info* info = nullptr) {
+    const int st = lsr_deskew_pc2(h_, data, n_points, &layout, scan_time, on_device ? 1 : 0, out_data, info);
+    report(st);
+    return st == LSR_OK;
+  }
   // align(output, ...) fills `output` with the transformed source like PCL does (12 bytes per point cross PCIe).  Both
   // reference callers discard it (scanmatcher_component.cpp:350-353, graph_based_slam_component.cpp:229-230): they switch
   // it off and `output` keeps the plain copy of the source pcl::Registration::align made.

@@ -17,6 +17,7 @@
 #include <cstddef>
 #include <cstring>
 #include <memory>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -85,6 +86,22 @@ class Registration {
   void setEuclideanFitnessEpsilon(double e) { check(lsr_set_f64(h_, LSR_EUCLIDEAN_FITNESS_EPSILON, e), "setEuclideanFitnessEpsilon"); }
   void setRANSACIterations(int n) { check(lsr_set_i32(h_, LSR_RANSAC_ITERATIONS, n), "setRANSACIterations"); }
   int getFinalNumIteration() const { return last_.iterations; }
+  // ---- IMU de-skew of the raw scan (use_imu) ----
+  // a fresh LidarUndistortion + setScanPeriod                       scanmatcher_component.cpp:80
+  void imuReset(double scan_period = 0.1) { check(lsr_imu_reset(h_, scan_period), "imuReset"); }
+  // ScanMatcherComponent::receiveImu                                scanmatcher_component.cpp:501-527
+  // sensor_msgs/Imu fields in message order (orientation x y z w); the library removes gravity as :505-511 does.  false: refused.
+  bool receiveImu(const double orientation_xyzw[4], const double angular_velocity[3], const double linear_acceleration[3], double stamp) {
+    return lsr_imu_receive(h_, orientation_xyzw, angular_velocity, linear_acceleration, stamp) == LSR_OK;
+  }
+  // lidar_undistortion_.adjustDistortion(tmp_ptr, scan_time)        scanmatcher_component.cpp:207
+  // raw PointCloud2 payload in, de-skewed payload out (host or device pointers, equal or disjoint)
+  bool deskewPointCloud2(const void* data, size_t n_points, const lsr_pc2_layout& layout, double scan_time, void* out_data,
+                         bool on_device = false, lsr_deskew_info* info = nullptr) {
+    const int st = lsr_deskew_pc2(h_, data, n_points, &layout, scan_time, on_device ? 1 : 0, out_data, info);
+    check(st, "deskewPointCloud2");
+    return st == LSR_OK;
+  }
   const lsr_result& lastResult() const { return last_; }
   lsr_handle handle() const { return h_; }
 

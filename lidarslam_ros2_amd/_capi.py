@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "lsr_shard_plan", "lsr_align_batch_planned", "lsr_align_fitness_batch",
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
+    "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
 ]
 
 
@@ -65,6 +66,10 @@ class LoopEdge(C.Structure):
 class Pc2Layout(C.Structure):
     _fields_ = [("point_step", C.c_uint32), ("offset_x", C.c_uint32), ("offset_y", C.c_uint32), ("offset_z", C.c_uint32),
                 ("offset_intensity", C.c_int32)]
+
+
+class DeskewInfo(C.Structure):
+    _fields_ = [("n_skipped", C.c_int32), ("start_missing", C.c_int32), ("half_index", C.c_int32), ("cursor", C.c_int32)]
 
 
 class ShardRecord(C.Structure):
@@ -157,6 +162,12 @@ def load() -> C.CDLL:
     i32p = C.POINTER(C.c_int32)
     L.lsr_shard_plan.argtypes = [C.c_int, dp, C.c_int, i32p, i32p, i32p]
     L.lsr_align_batch_planned.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, i32p, i32p, fp, C.c_int, C.POINTER(ShardRecord)]
+    L.lsr_imu_reset.argtypes = [vp, C.c_double]
+    L.lsr_imu_push.argtypes = [vp, fp, fp, fp, C.c_double]
+    L.lsr_imu_receive.argtypes = [vp, dp, dp, dp, C.c_double]
+    L.lsr_imu_info.argtypes = [vp, i32p]
+    L.lsr_deskew_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_int, vp, C.POINTER(DeskewInfo)]
+    L.lsr_deskew_trace.argtypes = [vp, fp, i32p, C.POINTER(C.c_uint8)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int or name not in ("lsr_version", "lsr_status_string", "lsr_last_error"):

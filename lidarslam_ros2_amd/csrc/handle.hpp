@@ -1,6 +1,7 @@
 // The opaque handle behind the C ABI (one registration object = one pcl::Registration instance).
 #pragma once
 #include "common.hpp"
+#include "deskew.hpp"
 #include "gicp.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
@@ -81,6 +82,8 @@ struct lsr_handle_s {
   PinBuf<lsr::FrameSlot> h_frames;   // ... and the pinned copy it is uploaded from
 
   GicpWorkspace gicp_ws;
+
+  lsr::DeskewState deskew;   // IMU queue and de-skew scratch (use_imu frontend path, csrc/deskew.hip)
 
   // worker objects of lsr_search_loop(top_k > 1): one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

@@ -8,6 +8,9 @@ tests/test_frontend_stream_gpu.py) and — through an adapter with the same meth
     every trans_for_mapupdate m  (updateMap) VoxelGrid(vg_size_for_map) of the scan (:442-446), kept with the registered pose as the newest
                                  submap (:466-478); target = that scan + the num_targeted_cloud - 1 submaps before it, each moved by its
                                  pose and concatenated (:448-464); setInputTarget at the start of the next callback (:304-307)
+    use_imu                      (:204-208) the raw payload is de-skewed once, on the device, before anything else reads it
+                                 (deskewPointCloud2); the de-skewed records feed the scan path AND the map side, as `tmp_ptr` does;
+                                 IMU messages arrive through receive_imu (:501-527)
     registration_method "GICP"   the same loop; the assembled window is put through VoxelGrid(vg_size_for_input) before setInputTarget
                                  (:308-316): setInputTargetFramesFiltered + prepareTarget (the target's covariances) on the map side
 
@@ -61,6 +64,8 @@ class FrontendParams:   # scanmatcher_component.cpp:36-60 (declare_parameter def
     scan_max_range: float = 100.0
     num_targeted_cloud: int = 10
     registration_method: str = "NDT"   # :98-125 — "NDT" or "GICP"
+    use_imu: bool = False              # :78 — de-skew the raw scan with the IMU queue before the range filter (:204-208)
+    scan_period: float = 0.1           # :80 — lidar_undistortion_.setScanPeriod
 
 
 @dataclass
@@ -103,6 +108,14 @@ class FrontendReplay:
         self.submaps: list = []          # [(payload as given to setInputTargetFrames, pose 4x4 f64)]
         self.pose = np.eye(4)
         self.key_position = np.zeros(3)
+        if self.p.use_imu:
+            self.reg.imuReset(self.p.scan_period)
+
+    def receive_imu(self, orientation_xyzw, angular_velocity, linear_acceleration, stamp: float) -> bool:
+        """One sensor_msgs/Imu message (receiveImu, :501-527); ignored unless use_imu (:503)."""
+        if not self.p.use_imu:
+            return False
+        return self.reg.receiveImu(orientation_xyzw, angular_velocity, linear_acceleration, stamp)
 
     def initialise(self, frames_xyz, frame_poses, pose0):
         """The map the drive starts from: the keyframes so far (sensor frame, already VoxelGrid(vg_size_for_map)-filtered) and their poses."""
@@ -153,7 +166,10 @@ class FrontendReplay:
                                                   self.p.vg_size_for_map)
             keyframe = self.mapper.getInputSourceDeviceRecords()
         else:
-            host = np.asarray(payload if payload_host is None else payload_host).reshape(n_points, step)
+            src = payload if payload_host is None else payload_host
+            if hasattr(src, "is_cuda") and src.is_cuda:
+                src = src.cpu().numpy()      # (a de-skewed device payload and no mapper object: the host-side filter needs a copy)
+            host = np.asarray(src).reshape(n_points, step)
             # updateMap filters the cloud the callback received, i.e. AFTER the subscription's range filter (:210-218: horizontal range,
             # open interval, in double) — a host-side mask here, as in the reference
             xy = host[:, :8].copy().view(np.float32).astype(np.float64)
@@ -184,11 +200,18 @@ class FrontendReplay:
         out.swap_at.append(self._n_scans)
         self._pending = None
 
-    def receive_cloud(self, payload, n_points: int, out: FrontendResult, payload_host=None):
+    def receive_cloud(self, payload, n_points: int, out: FrontendResult, payload_host=None, scan_time: Optional[float] = None):
         """One LiDAR message.  `payload`: the raw PointCloud2 data (host array or CUDA tensor); `payload_host`: a host copy for the map
-        update (the reference's callback holds the cloud on the host anyway); defaults to `payload`."""
+        update (the reference's callback holds the cloud on the host anyway); defaults to `payload`.  `scan_time`: the message's
+        header stamp [s]; needed with use_imu, where the payload is de-skewed first and the de-skewed records replace it for
+        everything that follows (the host copy included: the map side reads them back when it needs one)."""
         step, offs = PC2_XYZI
         t0 = time.perf_counter()
+        if self.p.use_imu:
+            if scan_time is None:
+                raise ValueError("use_imu needs the scan's header stamp (scan_time)")
+            payload, _ = self.reg.deskewPointCloud2(payload, n_points, step, offs, scan_time)
+            payload_host = None
         if self.async_update:
             self._settle(out)            # inside the scan's clock: what the callback really waits
         kept = self.reg.setInputSourcePointCloud2(payload, n_points, step, offs, self.p.scan_min_range, self.p.scan_max_range,

@@ -236,6 +236,63 @@ class Registration:
         self._n_source = int(n_out.value)
         return self._n_source
 
+    # -- IMU de-skew of the raw scan (use_imu: scanmatcher_component.cpp:204-208, 501-527) ---------------------------
+    def imuReset(self, scan_period: float = 0.1):
+        """A fresh LidarUndistortion with setScanPeriod(scan_period): empties the IMU ring of this object."""
+        capi.check(self._lib.lsr_imu_reset(self._h, float(scan_period)), "imuReset")
+
+    def receiveImu(self, orientation_xyzw, angular_velocity, linear_acceleration, stamp: float) -> bool:
+        """ScanMatcherComponent::receiveImu (scanmatcher_component.cpp:501-527) through lsr_imu_receive: the library removes gravity
+        from the linear acceleration with the roll / pitch of the orientation (:505-511) and pushes the sample into the ring.
+        orientation: geometry_msgs/Quaternion order x y z w.  False: the sample was refused (stamp out of order)."""
+        q, w, a = (np.ascontiguousarray(v, np.float64) for v in (orientation_xyzw, angular_velocity, linear_acceleration))
+        if q.shape != (4,) or w.shape != (3,) or a.shape != (3,):
+            raise ValueError("receiveImu takes orientation (4,), angular velocity (3,) and linear acceleration (3,)")
+        dp = C.POINTER(C.c_double)
+        st = self._lib.lsr_imu_receive(self._h, q.ctypes.data_as(dp), w.ctypes.data_as(dp), a.ctypes.data_as(dp), float(stamp))
+        return st == capi.OK
+
+    def imuInfo(self) -> dict:
+        info = np.zeros(4, np.int32)
+        capi.check(self._lib.lsr_imu_info(self._h, info.ctypes.data_as(C.POINTER(C.c_int32))), "imuInfo")
+        return dict(count=int(info[0]), last=int(info[1]), last_iter=int(info[2]))
+
+    def deskewPointCloud2(self, data, n_points: int, point_step: int, offsets, scan_time: float, out=None):
+        """lidar_undistortion_.adjustDistortion(cloud, scan_time) on a raw PointCloud2 `data` buffer (scanmatcher_component.cpp:207),
+        on the device: every point moves into the sensor frame of the scan's first point, every other byte of a record is copied.
+        `data`: uint8 numpy array / bytes (-> numpy array out) or CUDA uint8 tensor (-> CUDA tensor out, nothing leaves HBM).
+        `out`: None = a new buffer, or the buffer to write (`data` itself: in place).  Returns (records, info) with info =
+        dict(n_skipped, start_missing, half_index, cursor)."""
+        lay = self._layout(point_step, offsets)
+        info = capi.DeskewInfo()
+        n_points = int(n_points)
+        if _is_torch_cuda(data):
+            import torch
+
+            if out is None:
+                out = torch.empty_like(data)
+            _order_after_torch(self, data)
+            src, dst, dev = C.c_void_p(data.data_ptr()), C.c_void_p(out.data_ptr()), 1
+        else:
+            keep = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
+            if out is None:
+                out = np.empty_like(keep)
+            src, dst, dev = C.c_void_p(keep.ctypes.data), C.c_void_p(out.ctypes.data), 0
+        capi.check(self._lib.lsr_deskew_pc2(self._h, src, n_points, C.byref(lay), float(scan_time), dev, dst, C.byref(info)),
+                   "deskewPointCloud2")
+        self._n_deskew = n_points
+        return out, dict(n_skipped=int(info.n_skipped), start_missing=int(info.start_missing), half_index=int(info.half_index),
+                         cursor=int(info.cursor))
+
+    def deskewTrace(self) -> dict:
+        """Inspection (lsr_deskew_trace): what the last deskewPointCloud2 decided per point — rel_time (n,) fp32, the ring slot the IMU
+        pointer stood on (n,) int32 (-1 everywhere when that call moved nothing because the ring was too short), skipped (n,) uint8."""
+        n = int(getattr(self, "_n_deskew", 0))
+        rel, slot, sk = np.zeros(n, np.float32), np.full(n, -1, np.int32), np.zeros(n, np.uint8)
+        capi.check(self._lib.lsr_deskew_trace(self._h, rel.ctypes.data_as(C.POINTER(C.c_float)), slot.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              sk.ctypes.data_as(C.POINTER(C.c_uint8))), "deskewTrace")
+        return dict(rel_time=rel, slot=slot, skipped=sk)
+
     def voxelFilterForm(self) -> int:
         """Which form the last VoxelGrid filter on this object took (LSR_VOXEL_FILTER_FORM): 1 = grid dimensions on the host, 2 = on the
         device (one host wait per scan), 3 = the device form came back flagged and the host form ran; 0 = none yet."""
