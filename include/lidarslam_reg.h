@@ -66,6 +66,8 @@ typedef enum lsr_key {
   LSR_ROTATION_EPSILON = 5,           /* GICP rotation_epsilon_ (2e-3) */
   LSR_EUCLIDEAN_FITNESS_EPSILON = 6,  /* setEuclideanFitnessEpsilon         graph_based_slam_component.cpp:80 (no effect) */
   LSR_GICP_EPSILON = 7,               /* GICP gicp_epsilon_ (1e-3) */
+  LSR_MAP_ASSEMBLY_MS = 8,            /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the launches of the last
+                                         lsr_assemble_map on this object (the kernel alone: staging copies are outside the bracket); else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -103,10 +105,13 @@ typedef enum lsr_key {
                                          forms one half of the per-point neighbour tree; half the serial chain per wave, twice the waves),
                                          0 = one wave per chunk, -1 = automatic (= 0: measured on BASELINE cfg 5, the split form is not
                                          faster — the pass is bound by its fixed latency chain).  Environment preset LSR_NDT_SPLIT */
-  LSR_TARGET_PREPARED = 48            /* read-only (lsr_get_i32): 1 = an align with this object's parameters finds nothing left to build on
+  LSR_TARGET_PREPARED = 48,           /* read-only (lsr_get_i32): 1 = an align with this object's parameters finds nothing left to build on
                                          the current target (GICP: neighbour grid and k-NN covariances computed with this object's
                                          k_correspondences / gicp_epsilon; NDT: voxel grid at this object's resolution), 0 = the next
                                          align builds something first, or there is no target */
+  LSR_MAP_ASSEMBLY_FORM = 49          /* read-only (lsr_get_i32): which form the last lsr_assemble_map on this object took: 0 = none yet,
+                                         1 = wide (both layouts {32; 0,4,8,16}, every base pointer 16-byte aligned: two 16-byte loads
+                                         and two 16-byte stores per record), 2 = general (any layout).  The bytes are the same */
 } lsr_key;
 /* Environment presets read when an object is created: LSR_NDT_WORKGROUP, LSR_NDT_TABLE_MODE, LSR_NDT_QUAD, LSR_GRID_BUILDER,
  * LSR_WAIT_MODE (the keys above); LSR_NDT_CHAINS=1|2|3 fixes the number of independent launch chains a candidate set runs as (default: two
@@ -438,9 +443,39 @@ typedef struct lsr_loop_edge {
  * as its input target — the reference's state after the loop (:227) — whatever top_k was (with top_k > 1 the k windows are
  * built on worker objects and the nearest one's is handed to `h`), so a later getFitnessScore() on `h` scores exactly the
  * pose it reports.
- * The pose-graph optimisation that follows (doPoseAdjustment, g2o) is the caller's. */
+ * The pose-graph optimisation that follows (doPoseAdjustment, g2o) is the caller's; what the caller does with the optimiser's poses right
+ * afterwards — every submap moved by its new pose, the whole map put together — is lsr_assemble_map below. */
 int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, size_t stride_bytes, int on_device,
                     const lsr_loop_params* params, lsr_loop_edge* edges, int edge_capacity, int* n_evaluated);
+
+/* ---- the whole map from its submaps -------------------------------------- */
+/* ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of doPoseAdjustment
+ * (graph_based_slam_component.cpp:321-368): every submap of a lidarslam_msgs/MapArray is moved by its pose and the records are
+ * concatenated, submap after submap, record after record (`*map_ptr += ...`), in ONE launch over a device table of the submaps.
+ * submaps[i].cloud: n_points records of in_layout (x / y / z / intensity at its offsets; offset_intensity < 0: intensity 0), all host
+ * pointers (on_device == 0: staged through the handle's upload buffer in bounded pieces) or all HIP device pointers.
+ * Poses: poses16 == NULL — each submap's own position / orientation (tf2::fromMsg -> .matrix().cast<float>(), publishMap :538-542);
+ * poses16 != NULL — num_submaps column-major fp64 4x4 matrices instead (the optimiser's vertex->estimate(), :329-342), cast to float
+ * element by element.  A point is moved in fp32 as ((m00*x + m01*y) + m02*z) + m03, no FMA: the bits lsr_set_input_target_frames
+ * gives the same point and pose.  Non-finite coordinates are moved and written like any others; nothing is dropped.
+ * Output: records of out_layout, x' y' z' intensity at its offsets (offset_intensity < 0: not written), every other byte of a record
+ * zero, into out_data — a HIP device buffer (out_on_device != 0: the map stays in HBM) or a host buffer — of capacity_points records.
+ * *n_out = the sum of the n_points.  first_record (nullable, num_submaps + 1 entries): index of each submap's first record, the last
+ * entry the total — records [first_record[i], first_record[i+1]) are the moved cloud of submap i as it stands
+ * (modified_map_array.submaps[i].cloud, :343-351), no second pass.
+ * Appending: the call keeps no state.  submaps + k (and poses16 + 16 k) with out_data advanced by first_record[k] records writes
+ * exactly the records a call over all submaps writes there — a frontend whose old poses never change extends a resident map by its
+ * new keyframes only.
+ * Ordering and lifetime of device inputs: as for every device input above (reads on the handle's stream, lsr_wait_stream for a foreign
+ * producer).  Returns when the records are complete, for a reader on any stream.
+ * LSR_ERR_INVALID_ARGUMENT: null handle, layout, submaps or n_out; num_submaps <= 0; a point_step that is not a multiple of 4; a field
+ * that does not fit in its record; output fields that overlap; a pointer that is not 4-byte aligned; a submap with n_points > 0 and no
+ * cloud; capacity_points below the total; an output range that overlaps an input cloud.  LSR_ERR_INDEX_OVERFLOW: more than INT32_MAX
+ * records in all.  A total of zero is LSR_OK with *n_out = 0.  Outputs are left untouched on every error.
+ * LSR_MAP_ASSEMBLY_FORM tells which of the two kernel forms ran; the bytes do not depend on it, nor on where the buffers live. */
+int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
+                     const double* poses16 /* nullable */, void* out_data, size_t capacity_points,
+                     const lsr_pc2_layout* out_layout, int out_on_device, size_t* first_record /* nullable */, size_t* n_out);
 
 /* ---- inspection (parity tests / profiling; not used by the ROS nodes) ------------------- */
 /* NDT voxel grid: info[0..2]=min_b, [3..5]=max_b, [6]=#leaves (any point count), [7]=#leaves usable (n>=6, valid cov) */

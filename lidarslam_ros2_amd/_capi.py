@@ -17,9 +17,10 @@ OK = 0
 METHOD_NDT, METHOD_GICP = 0, 1
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
 (RESOLUTION, TRANSFORMATION_EPSILON, STEP_SIZE, OUTLIER_RATIO, MAX_CORRESPONDENCE_DISTANCE, ROTATION_EPSILON,
- EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON) = range(8)
+ EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON, MAP_ASSEMBLY_MS) = range(9)
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
- HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED) = range(32, 49)
+ HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED,
+ MAP_ASSEMBLY_FORM) = range(32, 50)
 
 EXPORTED_SYMBOLS = [
     "lsr_version", "lsr_status_string", "lsr_last_error", "lsr_device_count", "lsr_create", "lsr_destroy",
@@ -33,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
     "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
+    "lsr_assemble_map",
 ]
 
 
@@ -135,6 +137,8 @@ def load() -> C.CDLL:
     L.lsr_set_input_source_batch.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_int]
     L.lsr_search_loop.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.c_size_t, C.c_int, C.POINTER(LoopParams),
                                   C.POINTER(LoopEdge), C.c_int, ip]
+    L.lsr_assemble_map.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, vp, C.c_size_t, C.POINTER(Pc2Layout),
+                                   C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.lsr_ndt_grid_info.argtypes = [vp, ip]
     L.lsr_ndt_grid_dump.argtypes = [vp, ip, ip, dp, dp]
     L.lsr_ndt_grid_centroids.argtypes = [vp, fp]

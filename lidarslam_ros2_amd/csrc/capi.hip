@@ -919,6 +919,7 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_ROTATION_EPSILON: *v = h->gicp.rot_eps; return LSR_OK;
     case LSR_EUCLIDEAN_FITNESS_EPSILON: *v = h->euclidean_fitness_eps; return LSR_OK;
     case LSR_GICP_EPSILON: *v = h->gicp.gicp_eps; return LSR_OK;
+    case LSR_MAP_ASSEMBLY_MS: *v = h->map_ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -988,6 +989,7 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_GRID_BUILDER: *v = h->scratch.force_sort_path ? 1 : 0; return LSR_OK;
     case LSR_WAIT_MODE: *v = h->scratch.wait_mode; return LSR_OK;
     case LSR_VOXEL_FILTER_FORM: *v = h->scratch.vg_form; return LSR_OK;
+    case LSR_MAP_ASSEMBLY_FORM: *v = h->map_form; return LSR_OK;
     case LSR_TARGET_PREPARED:
       if (h->method == LSR_METHOD_GICP) *v = gicp_target_prepared(h) ? 1 : 0;
       else *v = (h->target && h->target->n > 0 && h->target->has_grid && h->target->grid_leaf == (float)h->ndt.resolution &&
@@ -1867,6 +1869,142 @@ int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, si
     (*n_evaluated)++;
   }
   return LSR_OK;
+}
+
+// ---- N5: the whole map from its submaps ---------------------------------------------------------
+// ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of doPoseAdjustment
+// (graph_based_slam_component.cpp:321-368).  One launch per piece: with every buffer on the device the whole map is one piece; a host
+// input or output is staged MAP_STAGE_BYTES at a time (a long submap is cut: a table slot is a run of records with a pose, not a submap).
+namespace {
+constexpr size_t MAP_STAGE_BYTES = (size_t)64 << 20;
+bool is_xyzi_layout(const lsr_pc2_layout* L) {
+  return L->point_step == 32 && L->offset_x == 0 && L->offset_y == 4 && L->offset_z == 8 && L->offset_intensity == 16;
+}
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a_bytes > 0 && b_bytes > 0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+}  // namespace
+
+int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
+                     const double* poses16, void* out_data, size_t capacity_points, const lsr_pc2_layout* out_layout, int out_on_device,
+                     size_t* first_record, size_t* n_out) {
+  LSR_CHECK_HANDLE(h);
+  if (!submaps || num_submaps <= 0 || !n_out) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
+  int st = check_layout(in_layout);
+  if (st) return st;
+  if ((st = check_layout(out_layout))) return st;
+  {
+    const int64_t f[4] = {(int64_t)out_layout->offset_x, (int64_t)out_layout->offset_y, (int64_t)out_layout->offset_z,
+                          out_layout->offset_intensity >= 0 ? (int64_t)out_layout->offset_intensity : (int64_t)-1};
+    for (int a = 0; a < 4; a++)
+      for (int b = a + 1; b < 4; b++)
+        if (f[a] >= 0 && f[a] == f[b]) { set_last_error("PointCloud2 layout: output fields overlap"); return LSR_ERR_INVALID_ARGUMENT; }
+  }
+  const size_t in_step = in_layout->point_step, out_step = out_layout->point_step;
+  const bool in_host = on_device == 0, out_host = out_on_device == 0;
+  size_t total = 0;
+  bool aligned16 = true;
+  for (int i = 0; i < num_submaps; i++) {
+    const lsr_submap& s = submaps[i];
+    if (s.n_points == 0) continue;
+    if (!s.cloud) { set_last_error("submap with points and a null cloud"); return LSR_ERR_INVALID_ARGUMENT; }
+    if ((uintptr_t)s.cloud & 3) { set_last_error("submap cloud is not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
+    if ((uintptr_t)s.cloud & 15) aligned16 = false;
+    if (s.n_points > (size_t)INT32_MAX || (total += s.n_points) > (size_t)INT32_MAX) {
+      set_last_error("the map holds more than INT32_MAX records");
+      return LSR_ERR_INDEX_OVERFLOW;
+    }
+  }
+  if (total > capacity_points) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (total > 0 && !out_data) { set_last_error("null output buffer"); return LSR_ERR_INVALID_ARGUMENT; }
+  if ((uintptr_t)out_data & 3) { set_last_error("output buffer is not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (in_host == out_host)
+    for (int i = 0; i < num_submaps; i++)
+      if (ranges_overlap(out_data, total * out_step, submaps[i].cloud, submaps[i].n_points * in_step)) {
+        set_last_error("the output range overlaps an input cloud");
+        return LSR_ERR_INVALID_ARGUMENT;
+      }
+  auto finish = [&]() {
+    if (first_record) {
+      size_t off = 0;
+      for (int i = 0; i < num_submaps; i++) { first_record[i] = off; off += submaps[i].n_points; }
+      first_record[num_submaps] = off;
+    }
+    *n_out = total;
+    return LSR_OK;
+  };
+  if (total == 0) return finish();
+
+  // poses: tf2::fromMsg -> Affine3d -> .cast<float>() (publishMap :538-542) or the optimiser's estimates (:329-342), cast the same way
+  std::vector<float> T((size_t)num_submaps * 16);
+  for (int i = 0; i < num_submaps; i++) {
+    double M[16];
+    if (poses16) std::memcpy(M, poses16 + 16 * (size_t)i, sizeof(M)); else submap_pose_matrix(submaps[i], M);
+    for (int k = 0; k < 16; k++) T[16 * (size_t)i + k] = (float)M[k];
+  }
+  // the wide form needs every base pointer on a 16-byte boundary; staged records are (32-byte records, back to back in a hipMalloc'ed buffer)
+  const bool wide = is_xyzi_layout(in_layout) && is_xyzi_layout(out_layout) && (in_host || aligned16) && (out_host || ((uintptr_t)out_data & 15) == 0);
+  MapLayouts L;
+  L.in_step = in_layout->point_step; L.in_x = in_layout->offset_x; L.in_y = in_layout->offset_y; L.in_z = in_layout->offset_z;
+  L.in_intensity = in_layout->offset_intensity;
+  L.out_step = out_layout->point_step; L.out_x = out_layout->offset_x; L.out_y = out_layout->offset_y; L.out_z = out_layout->offset_z;
+  L.out_intensity = out_layout->offset_intensity;
+
+  const size_t piece_cap = (in_host || out_host) ? std::max<size_t>(1, MAP_STAGE_BYTES / std::max(in_step, out_step)) : total;
+  if (in_host && (st = h->staging.reserve(std::min(total, piece_cap) * in_step))) return st;
+  if (out_host && (st = h->map_out.reserve(std::min(total, piece_cap) * out_step))) return st;
+  // whatever was enqueued has finished before the call returns: the table, the staging buffers and the caller's buffers are free again
+  struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{h->stream};
+  std::vector<MapSlot> slots;
+  double map_ms = 0.0;
+  size_t done = 0, at = 0;   // records written so far; position inside submap `i`
+  int i = 0;
+  while (done < total) {
+    slots.clear();
+    size_t piece = 0;
+    int n_slices = 0;
+    while (i < num_submaps && piece < piece_cap) {
+      const size_t left = submaps[i].n_points - at;
+      if (left == 0) { i++; at = 0; continue; }
+      const size_t take = std::min(left, piece_cap - piece);
+      const unsigned char* src = static_cast<const unsigned char*>(submaps[i].cloud) + at * in_step;
+      MapSlot S;
+      S.records = src;
+      if (in_host) {
+        S.records = h->staging.p + piece * in_step;
+        LSR_HIP(hipMemcpyAsync(h->staging.p + piece * in_step, src, take * in_step, hipMemcpyHostToDevice, h->stream));
+      }
+      S.first_out = (long long)((out_host ? 0 : done) + piece);
+      S.count = (int)take;
+      S.first_slice = n_slices;
+      std::memcpy(S.T16, T.data() + 16 * (size_t)i, sizeof(S.T16));
+      slots.push_back(S);
+      n_slices += (int)((take + MAP_SLICE - 1) / MAP_SLICE);
+      piece += take;
+      at += take;
+    }
+    if ((st = h->h_map_slots.reserve(slots.size()))) return st;
+    if ((st = h->d_map_slots.reserve(slots.size()))) return st;
+    std::memcpy(h->h_map_slots.p, slots.data(), sizeof(MapSlot) * slots.size());
+    LSR_HIP(hipMemcpyAsync(h->d_map_slots.p, h->h_map_slots.p, sizeof(MapSlot) * slots.size(), hipMemcpyHostToDevice, h->stream));
+    void* d_out = out_host ? static_cast<void*>(h->map_out.p) : out_data;
+    if (h->profile) LSR_HIP(hipEventRecord(h->ev0, h->stream));   // LSR_PROFILE: the launch alone, staging copies outside the bracket
+    if ((st = assemble_map(h->d_map_slots.p, (int)slots.size(), n_slices, wide, L, d_out, h->stream))) return st;
+    if (h->profile) LSR_HIP(hipEventRecord(h->ev1, h->stream));
+    if (out_host)
+      LSR_HIP(hipMemcpyAsync(static_cast<unsigned char*>(out_data) + done * out_step, h->map_out.p, piece * out_step, hipMemcpyDeviceToHost, h->stream));
+    LSR_HIP(hipStreamSynchronize(h->stream));   // the pinned table and the staging buffers are reused by the next piece
+    if (h->profile) {
+      float ms = 0.f;
+      LSR_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+      map_ms += ms;
+    }
+    done += piece;
+  }
+  h->map_form = wide ? 1 : 2;
+  h->map_ms = map_ms;
+  return finish();
 }
 
 int lsr_nearest_neighbors(lsr_handle h, const float* T16, int32_t* idx, float* d2) {

@@ -80,6 +80,11 @@ struct lsr_handle_s {
   DevBuf<float> d_poses;  // N2: keyframe poses
   DevBuf<lsr::FrameSlot> d_frames;   // N2, one-launch assembly: the window's frame table ...
   PinBuf<lsr::FrameSlot> h_frames;   // ... and the pinned copy it is uploaded from
+  DevBuf<lsr::MapSlot> d_map_slots;  // N5, lsr_assemble_map: the submap table of one launch ...
+  PinBuf<lsr::MapSlot> h_map_slots;  // ... and the pinned copy it is uploaded from
+  DevBuf<unsigned char> map_out;     // N5: a piece of the map on its way to a host buffer
+  int map_form = 0;                  // LSR_MAP_ASSEMBLY_FORM: 0 = none yet, 1 = wide, 2 = general
+  double map_ms = 0.0;               // LSR_MAP_ASSEMBLY_MS: hipEvent time of the last call's launches (LSR_PROFILE), else 0
 
   GicpWorkspace gicp_ws;
 

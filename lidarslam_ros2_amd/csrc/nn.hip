@@ -656,7 +656,118 @@ __global__ __launch_bounds__(256) void assemble_frames_bbox_kernel(const FrameSl
     __hip_atomic_store(&mb->part[blockIdx.x].g[k], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+
+// ---- N5: the whole map from its submaps — ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of
+// doPoseAdjustment (graph_based_slam_component.cpp:321-368): every submap moved by its pose, records concatenated in order.  Records in,
+// records out: x y z moved by frame_point_rn (the bits lsr_set_input_target_frames gives the same point and pose), intensity carried,
+// every other byte of the output record zero (pc2_write_kernel's convention).  Nothing is dropped: NaN in, NaN out.
+// The submaps are cut into slices of MAP_SLICE records; a workgroup walks the slices blockIdx.x, blockIdx.x + gridDim.x, ..., finds
+// the slot of a slice by binary search in the device table (uniform: scalar loads) and keeps four records per lane in flight.
+typedef float MapVec4 __attribute__((ext_vector_type(4)));   // a native vector: float4's operators take generic references only
+typedef MapVec4 __attribute__((address_space(1))) MapGlobalVec4;
+typedef float __attribute__((address_space(1))) MapGlobalFloat;
+typedef unsigned int __attribute__((address_space(1))) MapGlobalWord;
+typedef unsigned char __attribute__((address_space(1))) MapGlobalByte;
+__device__ __forceinline__ int map_slot_of_slice(const MapSlot* __restrict__ slots, int n_slots, int sl) {
+  int lo = 0, hi = n_slots - 1;   // the last slot whose first slice is <= sl (every slot owns at least one slice)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (slots[mid].first_slice <= sl) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// wide form: both layouts {32; 0,4,8,16}, every base pointer 16-byte aligned — a record is two 16-byte loads and two 16-byte stores
+__global__ __launch_bounds__(256) void assemble_map_wide_kernel(const MapSlot* __restrict__ slots, int n_slots, int n_slices,
+                                                                float4* __restrict__ out) {
+  const int tid = threadIdx.x;
+  for (int sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
+    const MapSlot& S = slots[map_slot_of_slice(slots, n_slots, sl)];
+    // the table holds plain pointers: say that they are global memory, or the loads below become flat ones
+    const MapGlobalVec4* __restrict__ rec = (const MapGlobalVec4*)S.records;
+    const int count = S.count, base = (sl - S.first_slice) * MAP_SLICE;
+    float4* __restrict__ dst = out + 2 * (size_t)S.first_out;
+    float T[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) T[k] = S.T16[k];
+    MapVec4 a[4], b[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = base + u * 256 + tid;
+      if (i < count) { a[u] = rec[2 * (size_t)i]; b[u] = rec[2 * (size_t)i + 1]; }
+      else { a[u] = MapVec4{0.f, 0.f, 0.f, 0.f}; b[u] = a[u]; }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = base + u * 256 + tid;
+      if (i >= count) continue;
+      float qx, qy, qz;
+      frame_point_rn(T, a[u].x, a[u].y, a[u].z, qx, qy, qz);
+      dst[2 * (size_t)i] = make_float4(qx, qy, qz, 0.f);
+      dst[2 * (size_t)i + 1] = make_float4(b[u].x, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
+// general form: any layout of 4-byte-aligned fields; the record is written word by word, fields where the layout puts them, zero elsewhere
+__global__ __launch_bounds__(256) void assemble_map_general_kernel(const MapSlot* __restrict__ slots, int n_slots, int n_slices,
+                                                                   const MapLayouts L, unsigned int* __restrict__ out) {
+  const int tid = threadIdx.x;
+  const unsigned int out_words = L.out_step >> 2, wx = L.out_x >> 2, wy = L.out_y >> 2, wz = L.out_z >> 2;
+  const unsigned int wi = L.out_intensity >= 0 ? (unsigned int)L.out_intensity >> 2 : 0xFFFFFFFFu;
+  for (int sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
+    const MapSlot& S = slots[map_slot_of_slice(slots, n_slots, sl)];
+    const MapGlobalByte* __restrict__ rec = (const MapGlobalByte*)S.records;
+    const int count = S.count, base = (sl - S.first_slice) * MAP_SLICE;
+    float T[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) T[k] = S.T16[k];
+    float p[4][3];
+    unsigned int it[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = base + u * 256 + tid;
+      p[u][0] = p[u][1] = p[u][2] = 0.f;
+      it[u] = 0u;
+      if (i < count) {
+        const MapGlobalByte* r = rec + (size_t)i * L.in_step;
+        p[u][0] = *(const MapGlobalFloat*)(r + L.in_x);
+        p[u][1] = *(const MapGlobalFloat*)(r + L.in_y);
+        p[u][2] = *(const MapGlobalFloat*)(r + L.in_z);
+        if (L.in_intensity >= 0) it[u] = *(const MapGlobalWord*)(r + L.in_intensity);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = base + u * 256 + tid;
+      if (i >= count) continue;
+      float qx, qy, qz;
+      frame_point_rn(T, p[u][0], p[u][1], p[u][2], qx, qy, qz);
+      unsigned int* o = out + ((size_t)S.first_out + (size_t)i) * out_words;
+      for (unsigned int w = 0; w < out_words; w++) {
+        unsigned int v = 0u;
+        if (w == wx) v = __float_as_uint(qx);
+        else if (w == wy) v = __float_as_uint(qy);
+        else if (w == wz) v = __float_as_uint(qz);
+        else if (w == wi) v = it[u];
+        o[w] = v;
+      }
+    }
+  }
+}
 }  // namespace
+
+int assemble_map(const MapSlot* d_slots, int n_slots, int n_slices, bool wide, const MapLayouts& L, void* d_out, hipStream_t stream) {
+  if (n_slots <= 0 || n_slices <= 0) return LSR_OK;
+  const int nb = std::min(n_slices, 2048);   // 256 CUs x 8 resident workgroups; the slices beyond are walked grid-stride
+  if (wide)
+    hipLaunchKernelGGL(assemble_map_wide_kernel, dim3(nb), dim3(256), 0, stream, d_slots, n_slots, n_slices, static_cast<float4*>(d_out));
+  else
+    hipLaunchKernelGGL(assemble_map_general_kernel, dim3(nb), dim3(256), 0, stream, d_slots, n_slots, n_slices, L,
+                       static_cast<unsigned int*>(d_out));
+  LSR_HIP(hipGetLastError());
+  return LSR_OK;
+}
 
 int transform_append(const void* d_aos, size_t stride_bytes, size_t n, const float* d_T16, DeviceCloud& out, size_t offset,
                      hipStream_t stream) {

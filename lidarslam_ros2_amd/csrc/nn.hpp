@@ -23,6 +23,25 @@ struct FrameSlot {
 int frames_slice_count(const size_t* counts, int n_frames, int* first_slice);
 int assemble_frames_bbox(const FrameSlot* d_frames, int n_frames, int n_slices, size_t stride_bytes, size_t total, DeviceCloud& out,
                          BuildScratch& sc, hipStream_t stream);
+// N5: the whole map from its submaps in one launch, records in, records out (lsr_assemble_map).  One table entry per submap (or
+// per piece of one), device resident; the output index is 64-bit, so the table has a slot type of its own.
+struct MapSlot {
+  const unsigned char* records;   // the submap's records in the input layout (device)
+  long long first_out;            // index of its first record in the output buffer
+  int count;                      // records of the slot (> 0: empty submaps get no slot)
+  int first_slice;                // index of its first slice of MAP_SLICE records
+  float T16[16];                  // column-major pose
+};
+struct MapLayouts {               // byte offsets; intensity < 0: the input has none / the output gets none
+  unsigned int in_step, in_x, in_y, in_z;
+  int in_intensity;
+  unsigned int out_step, out_x, out_y, out_z;
+  int out_intensity;
+};
+constexpr int MAP_SLICE = 1024;
+// wide: both layouts are pcl::PointXYZI's {32; 0,4,8,16} and every base pointer is 16-byte aligned (two 16-byte loads and two 16-byte
+// stores per record); otherwise the general form, any 4-byte-aligned layout.  Both write every byte of an output record.
+int assemble_map(const MapSlot* d_slots, int n_slots, int n_slices, bool wide, const MapLayouts& L, void* d_out, hipStream_t stream);
 float nn_pick_cell(size_t n, const lsr_handle_s* h);
 int nn_build_hash(const DeviceCloud& cloud, float cell, HashGridDev& grid, BuildScratch& sc, hipStream_t stream);
 // the same structure for NDT targets whose voxel grid was built by the counting-sort builder: a refinement of the voxel order

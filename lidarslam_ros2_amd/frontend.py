@@ -13,6 +13,9 @@ tests/test_frontend_stream_gpu.py) and — through an adapter with the same meth
                                  IMU messages arrive through receive_imu (:501-527)
     registration_method "GICP"   the same loop; the assembled window is put through VoxelGrid(vg_size_for_input) before setInputTarget
                                  (:308-316): setInputTargetFramesFiltered + prepareTarget (the target's covariances) on the map side
+    map_array                    (optional) the lidarslam_msgs/MapArray updateMap keeps (:466-481): every keyframe with the pose the message
+                                 stores and `latest_distance_ += trans_`; with map_publish_every = k every k-th update ends with
+                                 publishMap (:485-490, :529-552) — the new keyframes appended to a map that stays resident
 
 Nothing here computes: every step is one call into the registration object.
 
@@ -78,6 +81,7 @@ class FrontendResult:
     update_at: List[int] = field(default_factory=list)              # index of the scan after which each update was triggered
     swap_wait_seconds: List[float] = field(default_factory=list)    # asynchronous replay: what the due callback waited for the worker + the pointer swap
     swap_at: List[int] = field(default_factory=list)                # index of the scan whose callback took each new target over
+    publish_seconds: List[float] = field(default_factory=list)      # publishMap at the end of a map update (map_publish_every): extend_published
 
 
 class FrontendReplay:
@@ -86,7 +90,7 @@ class FrontendReplay:
     should be given (e.g. a CUDA tensor, so that the keyframes stay resident in HBM); identity when None."""
 
     def __init__(self, reg, params: FrontendParams | None = None, to_device=None, mapper=None, builder=None, async_update: bool = False,
-                 swap_lag: int = 0):
+                 swap_lag: int = 0, map_array=None, map_publish_every: int = 0):
         self.reg = reg
         self.p = params or FrontendParams()
         if self.p.registration_method not in ("NDT", "GICP"):
@@ -102,6 +106,17 @@ class FrontendReplay:
         if self.async_update and builder is None:
             raise ValueError("an asynchronous map update needs a builder object (the callback's object must not build targets)")
         self.swap_lag = int(swap_lag)
+        # `map_array` (optional): a lidarslam_ros2_amd.map_array.MapArray that receives every keyframe as a SubMap message would carry it
+        # (the window logic below keeps its own `self.submaps`); `map_publish_every` = k > 0: every k-th map update ends with publishMap.
+        # The reference's trigger is wall-clock (map_publish_period, :485-490); a replay must be deterministic, so updates are counted.
+        self.map_array = map_array
+        self.map_publish_every = int(map_publish_every)
+        if self.map_publish_every > 0 and map_array is None:
+            raise ValueError("map_publish_every needs a map_array")
+        self.published = None            # (records, first_record) of the last publishMap
+        self._latest_distance = 0.0      # latest_distance_ (:474)
+        self._n_updates = 0
+        self._publish_seconds: list = []
         self._pool = None
         self._pending = None             # (due scan index, future or job, trigger time)
         self._n_scans = 0
@@ -121,6 +136,12 @@ class FrontendReplay:
         """The map the drive starts from: the keyframes so far (sensor frame, already VoxelGrid(vg_size_for_map)-filtered) and their poses."""
         self.close()
         self.submaps = [(self.to_device(_records(as_pc2_payload(f))), np.asarray(P, np.float64)) for f, P in zip(frames_xyz, frame_poses)]
+        if self.map_array is not None:   # the MapArray holds the whole map, not the window: distance = path length over the keyframes
+            self._latest_distance, self._n_updates = 0.0, 0
+            for k, (rec, P) in enumerate(self.submaps):
+                if k:
+                    self._latest_distance += float(np.linalg.norm(P[:3, 3] - self.submaps[k - 1][1][:3, 3]))
+                self.map_array.append(rec, P, self._latest_distance)
         self.submaps = self.submaps[-self.p.num_targeted_cloud:]
         self._set_target()
         self._hand_over()
@@ -155,7 +176,7 @@ class FrontendReplay:
         if self.builder is not None:
             self.reg.shareTargetOf(self.builder)
 
-    def _update_job(self, payload, n_points, payload_host, T):
+    def _update_job(self, payload, n_points, payload_host, T, trans: float = 0.0):
         """updateMap (:436-481) up to and including the target of the next scans; -> seconds."""
         step, offs = PC2_XYZI
         t2 = time.perf_counter()
@@ -180,7 +201,17 @@ class FrontendReplay:
         self.submaps.append((keyframe, T.copy()))
         self.submaps = self.submaps[-self.p.num_targeted_cloud:]
         self._set_target()
-        return time.perf_counter() - t2
+        dt = time.perf_counter() - t2
+        if self.map_array is not None:
+            # :471-480 — latest_distance_ += trans_, the pose as the message stores it; :485-490 — publishMap, on its own clock
+            self._latest_distance += trans
+            self.map_array.append(keyframe, T, self._latest_distance)
+            self._n_updates += 1
+            if self.map_publish_every > 0 and self._n_updates % self.map_publish_every == 0:
+                t3 = time.perf_counter()
+                self.published = self.map_array.extend_published(self.builder or self.reg)
+                self._publish_seconds.append(time.perf_counter() - t3)
+        return dt
 
     def _settle(self, out: FrontendResult, force: bool = False):
         """Start of a callback (:298-320): a target that is due is taken over (the callback waits for the worker if it must)."""
@@ -195,6 +226,9 @@ class FrontendReplay:
         else:
             out.update_seconds.append(job())             # serial replay: the update runs here, between two scans
             t0 = time.perf_counter()
+        if self._publish_seconds:
+            out.publish_seconds.extend(self._publish_seconds)
+            self._publish_seconds = []
         self._hand_over()
         out.swap_wait_seconds.append(time.perf_counter() - t0)
         out.swap_at.append(self._n_scans)
@@ -224,10 +258,11 @@ class FrontendReplay:
         out.iterations.append(int(self.reg.getFinalNumIteration()))
         self._n_scans += 1
         # displacement since the last map update (:412-427): trans_ >= trans_for_mapupdate_ && !mapping_flag_
-        if self._pending is None and float(np.linalg.norm(T[:3, 3] - self.key_position)) >= self.p.trans_for_mapupdate:
+        trans = float(np.linalg.norm(T[:3, 3] - self.key_position))
+        if self._pending is None and trans >= self.p.trans_for_mapupdate:
             self.key_position = T[:3, 3].copy()
             out.update_at.append(len(out.poses) - 1)
-            job = (lambda p=payload, n=n_points, h=payload_host, TT=T.copy(): self._update_job(p, n, h, TT))
+            job = (lambda p=payload, n=n_points, h=payload_host, TT=T.copy(), d=trans: self._update_job(p, n, h, TT, d))
             if self.async_update:
                 if self._pool is None:
                     from concurrent.futures import ThreadPoolExecutor

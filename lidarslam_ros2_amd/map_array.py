@@ -1,0 +1,100 @@
+"""lidarslam_msgs/MapArray, host side: the list of SubMaps both nodes pass around, and what they do with it when they publish the map
+ — ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of
+GraphBasedSlamComponent::doPoseAdjustment (graph_based_slam_component.cpp:321-368) — behind `Registration.assembleMap`.
+
+The submaps are `loop_closure.SubMap`s, so `search_loop(reg, ma.submaps, ...)` takes them unchanged.  A pose is stored the way the
+message stores it: the position as given and the quaternion Eigen's Quaterniond(Matrix3d) makes of the rotation block
+(scanmatcher_component.cpp:394-398).  The map is moved by the pose that round trip yields (tf2::fromMsg, :538-542), not by the
+registration's float matrix: that is what the reference publishes.
+
+Nothing here computes on the points: every map is one call into the registration object.
+"""
+from __future__ import annotations
+
+from typing import List
+
+import numpy as np
+
+from .loop_closure import SubMap
+from .posemath import quaternion_from_matrix
+from .registration import PC2_XYZI, _is_torch_cuda
+
+
+def _as_float_records(records, point_step: int):
+    """A record buffer as the (n, point_step / 4) float32 view search_loop and setInputTargetFrames take (no copy)."""
+    if _is_torch_cuda(records):
+        import torch
+
+        t = records if records.is_contiguous() else records.contiguous()
+        if t.dtype == torch.float32 and t.dim() == 2:
+            return t
+        return t.view(-1).view(torch.uint8).view(-1, point_step).view(torch.float32)
+    a = np.ascontiguousarray(records)
+    if a.dtype == np.float32 and a.ndim == 2:
+        return a
+    return a.reshape(-1).view(np.uint8).reshape(-1, point_step).view(np.float32)
+
+
+class MapArray:
+    """`layout`: (point_step, (x, y, z, intensity or None)) of the submaps' records AND of the published map (pcl::PointXYZI's by default)."""
+
+    def __init__(self, layout=PC2_XYZI):
+        self.layout = layout
+        self.submaps: List[SubMap] = []
+        self._published = None        # resident buffer of extend_published: uint8, capacity * point_step bytes
+        self._published_submaps = 0   # submaps it holds
+        self._published_records = 0   # records it holds
+        self._first_record = [0]
+
+    def __len__(self) -> int:
+        return len(self.submaps)
+
+    def append(self, records, pose4x4, distance: float) -> SubMap:
+        """One SubMap message: `records` (pose-local, this object's layout; numpy array or CUDA tensor), the registered pose, the
+        accumulated travel distance (updateMap, scanmatcher_component.cpp:471-480)."""
+        P = np.asarray(pose4x4, np.float64)
+        sm = SubMap(cloud=_as_float_records(records, int(self.layout[0])), position=tuple(float(v) for v in P[:3, 3]),
+                    orientation=tuple(float(v) for v in quaternion_from_matrix(P[:3, :3])), distance=float(distance))
+        self.submaps.append(sm)
+        return sm
+
+    def publish_map(self, reg, out=None):
+        """publishMap (:529-552): every submap moved by its stored pose, concatenated.  -> (records, first_record)."""
+        return reg.assembleMap(self.submaps, None, self.layout, self.layout, out)
+
+    def modified_map(self, reg, poses, out=None):
+        """The map half of doPoseAdjustment (:321-368): every submap moved by the optimiser's estimate for it (4x4 fp64 each).
+        records[first_record[i]:first_record[i + 1]] is modified_map_array.submaps[i].cloud (:343-351).  -> (records, first_record)."""
+        return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
+
+    def extend_published(self, reg):
+        """publishMap for a frontend whose stored poses never change: only the submaps added since the last call are moved, appended to
+        a resident buffer that grows geometrically (on the device when the submaps are).  -> (records, first_record) of the whole map,
+        a view of that buffer, valid until the next call."""
+        step = int(self.layout[0])
+        new = self.submaps[self._published_submaps:]
+        if new:
+            add = int(sum(int(s.cloud.shape[0]) for s in new))
+            need = self._published_records + add
+            cap = 0 if self._published is None else self._published.shape[0] // step
+            if need > cap:
+                grown = self._empty(max(need, 2 * cap, 1) * step, any(_is_torch_cuda(s.cloud) for s in self.submaps), reg)
+                if self._published_records:
+                    grown[: self._published_records * step] = self._published[: self._published_records * step]
+                self._published = grown
+            _, first = reg.assembleMap(new, None, self.layout, self.layout, self._published[self._published_records * step:])
+            self._first_record += [self._published_records + int(v) for v in first[1:]]
+            self._published_submaps = len(self.submaps)
+            self._published_records = need
+        if self._published is None:
+            self._published = self._empty(step, False, reg)
+        n = self._published_records
+        return self._published[: n * step].reshape(n, step), np.array(self._first_record, np.int64)
+
+    @staticmethod
+    def _empty(nbytes: int, on_device: bool, reg):
+        if on_device:
+            import torch
+
+            return torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", getattr(reg, "_device", 0)))
+        return np.zeros(nbytes, np.uint8)

@@ -20,6 +20,7 @@ import numpy as np
 from . import _capi as capi
 
 DIRECT7, DIRECT1, DIRECT26, KDTREE = capi.DIRECT7, capi.DIRECT1, capi.DIRECT26, capi.KDTREE
+PC2_XYZI = (32, (0, 4, 8, 16))   # pcl::PointXYZI as pcl::toROSMsg lays it out: (point_step, (x, y, z, intensity or None))
 
 
 def _is_torch_cuda(x) -> bool:
@@ -46,6 +47,20 @@ def _cloud_args(cloud, reg=None):
         raise ValueError("cloud must have shape (n, c>=3)")
     a = np.ascontiguousarray(a, np.float32)
     return C.c_void_p(a.ctypes.data), a.shape[1] * 4, a.shape[0], False, a
+
+
+def _record_args(buf, point_step: int):
+    """A PointCloud2 payload as raw records -> (pointer, n_records, on_device, keepalive).  `buf`: numpy array or CUDA tensor of any
+    4-byte or 1-byte dtype, 1-D or (n, c), contiguous, whose bytes are whole records of `point_step`."""
+    if _is_torch_cuda(buf):
+        t = buf if buf.is_contiguous() else buf.contiguous()
+        nbytes, ptr, dev = t.numel() * t.element_size(), t.data_ptr(), True
+    else:
+        t = np.ascontiguousarray(buf)
+        nbytes, ptr, dev = t.nbytes, t.ctypes.data, False
+    if nbytes % point_step:
+        raise ValueError(f"buffer of {nbytes} bytes does not hold whole records of {point_step}")
+    return ptr, nbytes // point_step, dev, t
 
 
 def _mat_to_col16(M) -> np.ndarray:
@@ -345,6 +360,77 @@ class Registration:
         capi.check(self._lib.lsr_voxel_grid_filter(self._h, p, stride, n, C.c_float(leaf), C.c_void_p(out.ctypes.data), 12,
                                                    out.shape[0], C.byref(n_out)), "voxelGridFilter")
         return out[: n_out.value].copy()
+
+    # -- the whole map from its submaps ---------------------------------------------
+    def assembleMap(self, submaps, poses=None, in_layout=PC2_XYZI, out_layout=PC2_XYZI, out=None):
+        """ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of doPoseAdjustment
+        (graph_based_slam_component.cpp:321-368) through lsr_assemble_map: every submap moved by its pose, the records concatenated.
+        `submaps`: objects with `cloud`, `position`, `orientation` (x y z w) — loop_closure.SubMap; the clouds are record buffers
+        of `in_layout`, all numpy arrays or all CUDA tensors.  `poses`: None = each submap's own pose, or one 4x4 (fp64) per submap:
+        the optimiser's estimates.  Layouts: (point_step, (x, y, z, intensity or None)).  `out`: None = a new buffer, or the uint8
+        buffer to write (numpy array or CUDA tensor; a view of a resident map advanced by first_record[k] records appends).
+        Returns (records, first_record): (total, out point_step) uint8 — a CUDA tensor when the submaps are CUDA tensors or `out` is
+        one, else a numpy array — and the (n + 1,) int64 index of every submap's first record, the last entry the total."""
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("assembleMap needs at least one submap")
+        li, lo = self._layout(*in_layout), self._layout(*out_layout)
+        in_step, out_step = int(in_layout[0]), int(out_layout[0])
+        arr = (capi.SubMap * n)()
+        keep, residency = [], None
+        for i, sm in enumerate(submaps):
+            ptr, cnt, dev, holder = _record_args(sm.cloud, in_step)
+            keep.append(holder)
+            if cnt:
+                if residency is None:
+                    residency = dev
+                elif dev != residency:
+                    raise ValueError("all submap clouds must share residency (host/device)")
+            arr[i].position[:] = [float(v) for v in sm.position]
+            arr[i].orientation[:] = [float(v) for v in sm.orientation]
+            arr[i].distance = float(getattr(sm, "distance", 0.0))
+            arr[i].cloud = ptr if cnt else None
+            arr[i].n_points = cnt
+        if residency is None:
+            residency = any(_is_torch_cuda(h) for h in keep)
+        total = int(sum(a.n_points for a in arr))
+        P = None
+        if poses is not None:
+            if len(poses) != n:
+                raise ValueError("one pose per submap")
+            P = np.ascontiguousarray(np.stack([np.asarray(p, np.float64).reshape(4, 4).T.reshape(16) for p in poses]), np.float64)
+        if out is None:
+            if residency:
+                import torch
+
+                out = torch.empty((max(total, 1), out_step), dtype=torch.uint8, device=torch.device("cuda", self._device))
+            else:
+                out = np.zeros((max(total, 1), out_step), np.uint8)
+        out_dev = _is_torch_cuda(out)
+        if out_dev:
+            if not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out must be a contiguous uint8 buffer")
+            flat, optr, cap = out.view(-1), out.data_ptr(), out.numel() // out_step
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError("out must be a writeable contiguous uint8 buffer")
+            flat, optr, cap = out.reshape(-1), out.ctypes.data, out.nbytes // out_step
+        # ONE ordering of the handle's stream after torch's current stream, after every .contiguous() copy above has been enqueued there
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        if out_dev:
+            _order_after_torch(self, out)
+        first = (C.c_size_t * (n + 1))()
+        n_out = C.c_size_t()
+        capi.check(self._lib.lsr_assemble_map(self._h, arr, n, C.byref(li), 1 if residency else 0,
+                                              P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.c_void_p(optr), cap,
+                                              C.byref(lo), 1 if out_dev else 0, first, C.byref(n_out)), "assembleMap")
+        return flat[: n_out.value * out_step].reshape(n_out.value, out_step), np.array(first[:], np.int64)
+
+    def mapAssemblyForm(self) -> int:
+        """Which kernel form the last assembleMap on this object took (LSR_MAP_ASSEMBLY_FORM): 1 = wide, 2 = general; 0 = none yet."""
+        return self._geti(capi.MAP_ASSEMBLY_FORM)
 
     def shareTargetOf(self, other: "Registration"):
         """Register against the target already resident in `other` (N keyframes vs one submap)."""
