@@ -116,12 +116,8 @@ typedef enum lsr_key {
 /* Environment presets read when an object is created: LSR_NDT_WORKGROUP, LSR_NDT_TABLE_MODE, LSR_NDT_QUAD, LSR_GRID_BUILDER,
  * LSR_WAIT_MODE (the keys above); LSR_NDT_CHAINS=1|2|3 fixes the number of independent launch chains a candidate set runs as (default: two
  * from six members on, each on a stream verified to run concurrently with the object's own; LSR_DEBUG_STREAMS=1 prints what the
- * verification found).  Diagnostic A/B switches read once per process, all with bit-identical results (LSR_VG_DEVICE_DIMS=0: the
- * VoxelGrid filter always works out its grid dimensions on the host)
- * (tests/test_gicp_gpu.py::test_search_and_chain_variants_give_identical_results): LSR_NN_COOP=0 (per-thread neighbour
- * walks instead of one wave per query), LSR_GICP_FUSED=0 (accumulate + update launch pairs instead of the fused
- * Gauss-Newton step), LSR_GICP_BALL=0 (general correspondence search on every outer iteration), LSR_GICP_CORR_FUSED=0 (seeded
- * search, general search and pair records as three launches per outer iteration instead of one). */
+ * verification found).  Diagnostic A/B switch read once per process, with bit-identical results: LSR_VG_DEVICE_DIMS=0 (the
+ * VoxelGrid filter always works out its grid dimensions on the host). */
 
 typedef struct lsr_result {
   int32_t converged;            /* hasConverged()                             scanmatcher_component.cpp:375 */
@@ -501,7 +497,7 @@ int lsr_ndt_derivatives_pairs(lsr_handle h, const double* p6, const float* T16, 
 int lsr_gicp_covariances(lsr_handle h, int which, double* cov);
 /* GICP, one linearisation as lsr_align(h, guess16) runs it: the first correspondence pass and the first Gauss-Newton accumulation
  * of an outer iteration whose transformation_ is trans16 (col-major; NULL = identity, the first outer iteration), by the launches
- * of lsr_align itself (LSR_GICP_FUSED / LSR_GICP_CORR_FUSED / LSR_GICP_BALL / LSR_NN_COOP pick the form); nothing else of the outer
+ * of lsr_align itself; nothing else of the outer
  * iteration runs, and a later lsr_align returns what it would have returned without the call.  Inspection only (parity tests).
  * use_seeds != 0: the neighbours the previous lsr_align / lsr_gicp_linearize on this source and target left behind are offered as
  * search seeds, as from the second outer iteration on (LSR_ERR_INVALID_ARGUMENT when there are none).

@@ -34,12 +34,11 @@ struct GicpWorkspace {
   DevBuf<double> buf;            // per-workgroup partial rows + Rm
   DevBuf<unsigned char> state;   // per-iteration block {GnState, T16, Rm} + counters
   PinBuf<unsigned char> pin;     // pinned host mirror of the per-iteration block
-  DevBuf<int> work;              // K5: count + indices of the points deferred to the wave-cooperative search
+  DevBuf<int> work;              // K5: the k neighbours of every point, nearest first (search kernel -> covariance kernel)
   DevBuf<double> raw_cov;        // inspection only: sample covariances before regularisation
   DevBuf<int> last_nn;           // K6: each source point's neighbour in the previous outer iteration (search seed)
-  DevBuf<float> nn_d2;           // K6: its squared distance (search kernel -> pair kernel)
-  DevBuf<int> corr_work;         // K6: [0] = count, [1..] = points the seeded search hands to the general one
-  DevBuf<int> count_shards;      // K6: pair counters of the one-launch correspondence pass, a cache line apart
+  DevBuf<float> nn_d2;           // K6: its squared distance
+  DevBuf<int> count_shards;      // K6: pair counters of the correspondence pass, a cache line apart
   PinBuf<GicpMailbox> mailbox;
   GicpMailbox* d_mailbox = nullptr;
   unsigned int token = 0;        // one per align

@@ -279,37 +279,6 @@ __global__ __launch_bounds__(NN_THREADS) void nn1_kernel(NNGridView G, const flo
   d2[i] = c.d2;
 }
 
-// The same first stage on four lanes per query (nn1_query_quad): a quarter of the dependent-load chain per lane.
-__device__ __forceinline__ void nn1_quad_body(const NNGridView& G, const float* __restrict__ qx, const float* __restrict__ qy,
-                                              const float* __restrict__ qz, int n, const float* __restrict__ T16, int fine_rings, int ring_cap,
-                                              float max_d2, int* __restrict__ work, int* __restrict__ idx, float* __restrict__ d2, const int t) {
-  const int i = t >> 2, sub = t & 3;
-  if (i >= n) return;   // n * 4 threads: a quad is never split by this test
-  const float x = qx[i], y = qy[i], z = qz[i];
-  float tx = x, ty = y, tz = z;
-  if (T16) {
-    tx = xform_rn(T16[0], T16[4], T16[8], T16[12], x, y, z);
-    ty = xform_rn(T16[1], T16[5], T16[9], T16[13], x, y, z);
-    tz = xform_rn(T16[2], T16[6], T16[10], T16[14], x, y, z);
-  }
-  Best1 c;
-  c.init();
-  const bool proven = nn1_query_quad(G, tx, ty, tz, fine_rings, max_d2, c, ring_cap, sub);
-  if (sub != 0) return;
-  if (!proven) {
-    work[1 + atomicAdd(work, 1)] = i;
-    return;
-  }
-  idx[i] = c.idx;
-  d2[i] = c.d2;
-}
-__global__ __launch_bounds__(NN_THREADS) void nn1_quad_kernel(NNGridView G, const float* __restrict__ qx, const float* __restrict__ qy,
-                                                              const float* __restrict__ qz, int n, const float* __restrict__ T16,
-                                                              int fine_rings, int ring_cap, float max_d2, int* __restrict__ work,
-                                                              int* __restrict__ idx, float* __restrict__ d2) {
-  nn1_quad_body(G, qx, qy, qz, n, T16, fine_rings, ring_cap, max_d2, work, idx, d2, blockIdx.x * blockDim.x + threadIdx.x);
-}
-
 // One wave per query (coop_search over the fine grid, coarse cells when needed): the form used for scan-sized query sets.
 __device__ __forceinline__ void nn1_wave_body(const NNGridView& G, const float* __restrict__ qx, const float* __restrict__ qy,
                                               const float* __restrict__ qz, int n, const float* __restrict__ T16, int fine_rings,
@@ -388,23 +357,6 @@ __global__ __launch_bounds__(256) void nn1_coop_kernel(NNGridView G, const float
   nn1_coop_body(G, qx, qy, qz, T16, max_d2, work, idx, d2, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
 }
 
-__global__ __launch_bounds__(NN_THREADS) void knn_kernel(NNGridView G, const float* __restrict__ qx, const float* __restrict__ qy,
-                                                         const float* __restrict__ qz, int n, int k, int fine_rings,
-                                                         int* __restrict__ idx, float* __restrict__ d2) {
-  extern __shared__ unsigned char smem[];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  BestK c;
-  c.init(smem, threadIdx.x, k);
-  if (i < n) {
-    nn_query(G, qx[i], qy[i], qz[i], fine_rings, INFINITY, c, -1);
-    c.finalize();
-    for (int s = 0; s < k; s++) {
-      idx[(size_t)i * k + s] = c.index(s);
-      d2[(size_t)i * k + s] = c.dist(s);
-    }
-  }
-}
-
 // deterministic two-stage reduction of {sum d2, count} over pairs with d2 <= max_range
 __device__ __forceinline__ void fitness_partial_body(const int* __restrict__ idx, const float* __restrict__ d2, int n, double max_range,
                                                      double* __restrict__ part, const int blk, const int nblk) {
@@ -459,7 +411,7 @@ __global__ void fit_zero_work_group_kernel(const FitGroup g) { g.m[threadIdx.x].
 //   2. every point at distance <= d lies in a fine cell that touches the ball of radius d around the query (the cell index is a
 //      monotone map; the reach is padded against rounding: ball_cell_range): those cells — one to eight for a registered scan, not the
 //      27 of a shell — are ALL that is left to read, one lane per (row, coarse segment), candidates laid end to end, 16 per round
-//      (the structure of gicp_corr_ball_kernel, whose seed is the previous outer iteration's neighbour);
+//      (the structure of gicp_corr_seeded_kernel, whose seed is the previous outer iteration's neighbour);
 //   3. a query with no point within a cell of it, or whose ball spans more than FIT_BALL_CELLS cells on an axis, goes on the
 //      member's work list for the general one-wave-per-query search (nn1_list_group_kernel): exact all the same.
 // Same candidates compared in the same total order (distance, index), same fp32 distances => the answer of every other search
@@ -972,11 +924,6 @@ int nn_build_hash_from_grids(const VoxelGridDev* const* vgrids, HashGridDev* con
   return LSR_OK;
 }
 
-bool nn_coop_enabled() {
-  static const bool on = [] { const char* e = getenv("LSR_NN_COOP"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 int nn_search_device(const DeviceCloud& q, const float* d_T16, const HashGridDev& grid, int fine_rings, float max_d2,
                      int* d_idx, float* d_d2, hipStream_t stream, int* d_work) {
   const int n = (int)q.n;
@@ -989,36 +936,19 @@ int nn_search_device(const DeviceCloud& q, const float* d_T16, const HashGridDev
   // d_work (n + 1 ints) given: two-stage search — per-thread walk capped at two fine shells, wave-cooperative tail
   const int ring_cap = d_work ? 2 : -1;
   const int spread = (d_work && n <= 65536) ? 2 : 1;
-  if (d_work && n <= 262144 && nn_coop_enabled()) {   // small query sets (a scan): one wave per query
+  if (d_work && n <= 262144) {   // small query sets (a scan): one wave per query
     hipLaunchKernelGGL(nn1_wave_kernel, dim3((unsigned)(((long)n * 64 + 255) / 256)), dim3(256), 0, stream, make_view(grid), q.x(), q.y(),
                        q.z(), n, d_T16, fine_rings, max_d2, d_idx, d_d2);
     LSR_HIP(hipGetLastError());
     return LSR_OK;
   }
   if (d_work) LSR_HIP(hipMemsetAsync(d_work, 0, sizeof(int), stream));
-  if (d_work && n <= 262144) {   // small query sets (a scan): four lanes per query
-    const long threads = (long)n * 4;
-    hipLaunchKernelGGL(nn1_quad_kernel, dim3((unsigned)((threads + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, stream,
-                       make_view(grid), q.x(), q.y(), q.z(), n, d_T16, fine_rings, ring_cap, max_d2, d_work, d_idx, d_d2);
-  } else {
-    const long threads = (long)n * spread;
-    hipLaunchKernelGGL(nn1_kernel, dim3((unsigned)((threads + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, stream, make_view(grid),
-                       q.x(), q.y(), q.z(), n, d_T16, fine_rings, ring_cap, spread, max_d2, d_work, d_idx, d_d2);
-  }
+  const long threads = (long)n * spread;
+  hipLaunchKernelGGL(nn1_kernel, dim3((unsigned)((threads + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0, stream, make_view(grid),
+                     q.x(), q.y(), q.z(), n, d_T16, fine_rings, ring_cap, spread, max_d2, d_work, d_idx, d_d2);
   if (d_work)
     hipLaunchKernelGGL(nn1_coop_kernel, dim3(1024), dim3(256), 0, stream, make_view(grid), q.x(), q.y(), q.z(), d_T16, max_d2, d_work,
                        d_idx, d_d2);
-  LSR_HIP(hipGetLastError());
-  return LSR_OK;
-}
-
-int knn_search_device(const DeviceCloud& q, const HashGridDev& grid, int k, int fine_rings, int* d_idx, float* d_d2,
-                      hipStream_t stream) {
-  const int n = (int)q.n;
-  if (n == 0) return LSR_OK;
-  const size_t smem = BestK::lds_bytes(k);
-  hipLaunchKernelGGL(knn_kernel, dim3((n + NN_THREADS - 1) / NN_THREADS), dim3(NN_THREADS), smem, stream, make_view(grid), q.x(),
-                     q.y(), q.z(), n, k, fine_rings, d_idx, d_d2);
   LSR_HIP(hipGetLastError());
   return LSR_OK;
 }

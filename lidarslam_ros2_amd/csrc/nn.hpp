@@ -50,19 +50,15 @@ int nn_build_hash_from_grids(const VoxelGridDev* const* vgrids, HashGridDev* con
 // mean squared 1-NN distance of T*source in the target, over pairs with d2 <= max_range.
 int nn_fitness_score(const DeviceCloud& source, const float* T16_host, const HashGridDev& grid, double max_range, double* out,
                      BuildScratch& sc, DevBuf<float>& d_T16, hipStream_t stream);
-// A/B switch for the wave-cooperative searches (env LSR_NN_COOP=0 selects the per-thread walks); read once.
-bool nn_coop_enabled();
 int nn_fitness_begin(const DeviceCloud& source, const float* T16_host, const HashGridDev& grid, double max_range, BuildScratch& sc,
                      DevBuf<float>& d_T16, hipStream_t stream);
 int nn_fitness_end(BuildScratch& sc, hipStream_t stream, double* out);
 // the search + reduction of a set of candidates in group launches on one stream (each member: its own scratch and mailbox)
 struct FitJob { const DeviceCloud* source; const float* T16; const HashGridDev* grid; double max_range; BuildScratch* sc; };
 int nn_fitness_begin_group(const FitJob* jobs, int count, hipStream_t stream);
-// Device-side entry points (results stay in HBM): 1-NN of T*q (T nullable) and k-NN of q.
+// Device-side entry point (results stay in HBM): 1-NN of T*q (T nullable).
 int nn_search_device(const DeviceCloud& q, const float* d_T16, const HashGridDev& grid, int fine_rings, float max_d2,
                      int* d_idx, float* d_d2, hipStream_t stream, int* d_work = nullptr);  // d_work: n + 1 ints => two-stage search
-int knn_search_device(const DeviceCloud& q, const HashGridDev& grid, int k, int fine_rings, int* d_idx, float* d_d2,
-                      hipStream_t stream);
 int nn_search_host(const DeviceCloud& source, const float* T16_host, const HashGridDev& grid, int32_t* idx, float* d2,
                    BuildScratch& sc, DevBuf<float>& d_T16, hipStream_t stream);
 }  // namespace lsr

@@ -5,9 +5,6 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/switch_matrix; rm -rf $O; mkdir -p $O
 run() { name=$1; shift; (env "$@" timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -3) > $O/$name.log; echo "$name: $(tail -1 $O/$name.log | cut -c1-120)"; }
 run default LSR_NOP=1
-run nn_coop0 LSR_NN_COOP=0
-run gicp_fused0 LSR_GICP_FUSED=0
-run gicp_ball0 LSR_GICP_BALL=0
 run ndt_quad0 LSR_NDT_QUAD=0
 run wait_sleep LSR_WAIT_MODE=sleep
 run wait_yield LSR_WAIT_MODE=yield
