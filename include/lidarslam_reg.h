@@ -439,8 +439,9 @@ typedef struct lsr_loop_edge {
  * as its input target — the reference's state after the loop (:227) — whatever top_k was (with top_k > 1 the k windows are
  * built on worker objects and the nearest one's is handed to `h`), so a later getFitnessScore() on `h` scores exactly the
  * pose it reports.
- * The pose-graph optimisation that follows (doPoseAdjustment, g2o) is the caller's; what the caller does with the optimiser's poses right
- * afterwards — every submap moved by its new pose, the whole map put together — is lsr_assemble_map below. */
+ * The pose-graph optimisation that follows (doPoseAdjustment, :267-319) is lsr_optimize_pose_graph below — no g2o needed —, and what the
+ * caller does with the optimiser's poses right afterwards — every submap moved by its new pose, the whole map put together — is
+ * lsr_assemble_map. */
 int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, size_t stride_bytes, int on_device,
                     const lsr_loop_params* params, lsr_loop_edge* edges, int edge_capacity, int* n_evaluated);
 
@@ -472,6 +473,62 @@ int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, si
 int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
                      const double* poses16 /* nullable */, void* out_data, size_t capacity_points,
                      const lsr_pc2_layout* out_layout, int out_on_device, size_t* first_record /* nullable */, size_t* n_out);
+
+/* ---- pose-graph optimisation --------------------------------------------- */
+/* The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319): g2o's VertexSE3 / EdgeSE3 graph with identity
+ * information, vertex 0 fixed, under g2o's Levenberg-Marquardt controller, restated in fp64 (DESIGN.md 4 "Pose-graph optimisation") and solved on the device. */
+#define LSR_POSE_GRAPH_MAX_VERTICES 8192
+#define LSR_POSE_GRAPH_MAX_BAND 8
+#define LSR_POSE_GRAPH_MAX_OFFBAND_EDGES 64
+typedef struct lsr_pose_edge {
+  int32_t from, to;             /* EdgeSE3::vertices()[0], [1] */
+  double measurement[16];       /* from^-1 * to, column-major 4x4 fp64: the layout of lsr_loop_edge.relative_pose */
+} lsr_pose_edge;
+typedef struct lsr_pose_graph_params {
+  int32_t max_iterations;       /* [10] optimizer.optimize(10) (:318); 1 or more */
+  int32_t band;                 /* [5]  edges with |from - to| <= band form the block band of the solve (1 .. LSR_POSE_GRAPH_MAX_BAND);
+                                 *      it changes where an edge is summed, not the system that is solved: use num_adjacent */
+} lsr_pose_graph_params;
+enum {
+  LSR_POSE_GRAPH_STOP_MAX_ITERATIONS = 0,  /* all max_iterations ran */
+  LSR_POSE_GRAPH_STOP_TRIALS = 1,          /* ten trials of one iteration were rejected */
+  LSR_POSE_GRAPH_STOP_RHO_ZERO = 2,        /* the gain ratio was exactly zero */
+  LSR_POSE_GRAPH_STOP_LAMBDA = 3           /* lambda left the finite numbers */
+};
+typedef struct lsr_pose_graph_result {
+  int32_t iterations;           /* iterations run */
+  int32_t trials;               /* solves in all (accepted and rejected) */
+  double chi2_before;           /* sum e^T e at the incoming poses (no factor 1/2) */
+  double chi2_after;            /* ... at the returned poses */
+  double lambda;                /* the damping after the last iteration */
+  int32_t stop_reason;          /* LSR_POSE_GRAPH_STOP_* */
+  int32_t reserved;
+  double device_ms;             /* hipEvent time from the first upload to the last read-back on the object's stream */
+} lsr_pose_graph_result;
+typedef struct lsr_pose_graph_trace {
+  int32_t trials;               /* solves of this iteration */
+  int32_t reserved;
+  double chi2, lambda, rho;     /* after the iteration: accepted chi2, damping, the last gain ratio */
+} lsr_pose_graph_trace;
+/* The odometry edges doPoseAdjustment adds (:289-303), in its order: for every i > num_adjacent (strictly) and j = 0 .. num_adjacent-1
+ * the edge (i - num_adjacent + j -> i) measured from the incoming poses (poses16: n column-major fp64 4x4).  Vertices 0 .. num_adjacent
+ * get none, as there.  Host only, needs no device.  *n_out = the number of edges; more than `capacity` of them: LSR_ERR_INVALID_ARGUMENT
+ * with *n_out set and `out` untouched.  Null poses16 / n_out, n < 1 or num_adjacent < 1: LSR_ERR_INVALID_ARGUMENT. */
+int lsr_pose_graph_edges(const double* poses16, int n, int num_adjacent, lsr_pose_edge* out, size_t capacity, size_t* n_out);
+/* optimizer.initializeOptimization(); optimizer.optimize(max_iterations) (:317-318) over n vertices (poses16_in, vertex 0 fixed) and
+ * n_edges edges — the caller passes the odometry edges (lsr_pose_graph_edges) followed by one edge per accumulated loop edge
+ * (from = id_from, to = id_to, measurement = relative_pose; :308-315); a pair may occur twice.  poses16_out: n column-major fp64 4x4,
+ * what lsr_assemble_map takes as poses16 (may be poses16_in).  params NULL = the defaults in brackets.  trace (nullable): room for
+ * max_iterations entries, one written per iteration run.  The linear solve is exact (band Cholesky + Woodbury over the edges outside
+ * the band; an edge into vertex 0 counts as inside); a host loop reads a few scalars per trial.  Results do not depend on `band`
+ * beyond rounding and are bit-identical from call to call.
+ * LSR_ERR_INVALID_ARGUMENT: null handle, poses, edges (with n_edges > 0), poses16_out or result; n < 1; n > LSR_POSE_GRAPH_MAX_VERTICES;
+ * n_edges < 0 or above 2^20; an edge with from == to or an index outside [0, n); max_iterations < 1; band outside
+ * 1 .. LSR_POSE_GRAPH_MAX_BAND; more than LSR_POSE_GRAPH_MAX_OFFBAND_EDGES edges outside the band.  LSR_ERR_HIP: a HIP call failed, or
+ * the host could not allocate its copy of the graph.  Outputs are untouched on every error.  n == 1 or n_edges == 0: LSR_OK, the input poses, zero iterations.  Writing pose_graph.g2o (:319) stays the caller's. */
+int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
+                            const lsr_pose_graph_params* params /* nullable */, double* poses16_out, lsr_pose_graph_result* result,
+                            lsr_pose_graph_trace* trace /* nullable */);
 
 /* ---- inspection (parity tests / profiling; not used by the ROS nodes) ------------------- */
 /* NDT voxel grid: info[0..2]=min_b, [3..5]=max_b, [6]=#leaves (any point count), [7]=#leaves usable (n>=6, valid cov) */

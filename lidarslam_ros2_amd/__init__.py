@@ -8,7 +8,8 @@ from .registration import (DIRECT1, DIRECT7, DIRECT26, KDTREE, GeneralizedIterat
                            NormalDistributionsTransform, Registration, align_batch)
 from .loop_closure import LoopClosureParams, LoopEdge, SubMap, search_loop
 from .map_array import MapArray
+from . import pose_graph
 
 __all__ = ["Registration", "NormalDistributionsTransform", "GeneralizedIterativeClosestPoint", "align_batch",
-           "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray",
+           "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray", "pose_graph",
            "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("LSR_LIB_NAME", "liblidarslam_reg.
 
 # enums (mirror include/lidarslam_reg.h)
 OK = 0
+POSE_GRAPH_MAX_VERTICES, POSE_GRAPH_MAX_BAND, POSE_GRAPH_MAX_OFFBAND_EDGES = 8192, 8, 64
 METHOD_NDT, METHOD_GICP = 0, 1
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
 (RESOLUTION, TRANSFORMATION_EPSILON, STEP_SIZE, OUTLIER_RATIO, MAX_CORRESPONDENCE_DISTANCE, ROTATION_EPSILON,
@@ -34,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
     "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
-    "lsr_assemble_map",
+    "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph",
 ]
 
 
@@ -63,6 +64,23 @@ class LoopEdge(C.Structure):
     _fields_ = [("id_from", C.c_int), ("id_to", C.c_int), ("accepted", C.c_int), ("converged", C.c_int),
                 ("iterations", C.c_int), ("n_target_points", C.c_int), ("candidate_distance", C.c_double),
                 ("fitness_score", C.c_double), ("relative_pose", C.c_double * 16), ("final_transformation", C.c_float * 16)]
+
+
+class PoseEdge(C.Structure):
+    _fields_ = [("from_", C.c_int32), ("to", C.c_int32), ("measurement", C.c_double * 16)]
+
+
+class PoseGraphParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("band", C.c_int32)]
+
+
+class PoseGraphResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_before", C.c_double), ("chi2_after", C.c_double),
+                ("lam", C.c_double), ("stop_reason", C.c_int32), ("reserved", C.c_int32), ("device_ms", C.c_double)]
+
+
+class PoseGraphTrace(C.Structure):
+    _fields_ = [("trials", C.c_int32), ("reserved", C.c_int32), ("chi2", C.c_double), ("lam", C.c_double), ("rho", C.c_double)]
 
 
 class Pc2Layout(C.Structure):
@@ -139,6 +157,9 @@ def load() -> C.CDLL:
                                   C.POINTER(LoopEdge), C.c_int, ip]
     L.lsr_assemble_map.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, vp, C.c_size_t, C.POINTER(Pc2Layout),
                                    C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.lsr_pose_graph_edges.argtypes = [dp, C.c_int, C.c_int, C.POINTER(PoseEdge), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lsr_optimize_pose_graph.argtypes = [vp, dp, C.c_int, C.POINTER(PoseEdge), C.c_int, C.POINTER(PoseGraphParams), dp,
+                                          C.POINTER(PoseGraphResult), C.POINTER(PoseGraphTrace)]
     L.lsr_ndt_grid_info.argtypes = [vp, ip]
     L.lsr_ndt_grid_dump.argtypes = [vp, ip, ip, dp, dp]
     L.lsr_ndt_grid_centroids.argtypes = [vp, fp]

@@ -2007,6 +2007,52 @@ int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, c
   return finish();
 }
 
+int lsr_pose_graph_edges(const double* poses16, int n, int num_adjacent, lsr_pose_edge* out, size_t capacity, size_t* n_out) {
+  if (!poses16 || !n_out || n < 1 || num_adjacent < 1) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
+  return pose_graph_adjacent_edges(poses16, n, num_adjacent, out, capacity, n_out);   // allocates nothing
+}
+
+int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
+                            const lsr_pose_graph_params* params, double* poses16_out, lsr_pose_graph_result* result,
+                            lsr_pose_graph_trace* trace) {
+  LSR_CHECK_HANDLE(h);
+  if (!poses16_in || !poses16_out || !result || n < 1 || n_edges < 0 || (n_edges > 0 && !edges)) {
+    set_last_error("bad argument");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  const int max_iterations = params ? params->max_iterations : 10, band = params ? params->band : 5;
+  if (n > PG_MAX_VERTICES || n_edges > PG_MAX_EDGES || max_iterations < 1 || band < 1 || band > PG_MAX_BAND) {
+    set_last_error("pose graph: vertices, edges, max_iterations or band outside the documented limits");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  int off_band = 0;
+  for (int k = 0; k < n_edges; k++) {
+    const int a = edges[k].from, b = edges[k].to;
+    if (a < 0 || b < 0 || a >= n || b >= n || a == b) {
+      set_last_error("pose graph: edge " + std::to_string(k) + " joins a vertex to itself or names one that does not exist");
+      return LSR_ERR_INVALID_ARGUMENT;
+    }
+    if (a != 0 && b != 0 && std::abs(a - b) > band) off_band++;
+  }
+  if (off_band > PG_MAX_OFFBAND) {
+    set_last_error("pose graph: more than LSR_POSE_GRAPH_MAX_OFFBAND_EDGES edges outside the band");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 1 || n_edges == 0) {
+    if (poses16_out != poses16_in) std::memmove(poses16_out, poses16_in, sizeof(double) * 16 * (size_t)n);
+    std::memset(result, 0, sizeof(*result));
+    return LSR_OK;
+  }
+  // the host side of the graph lives in std::vectors (up to 2^20 edges): nothing they throw crosses the C ABI
+  try {
+    return pose_graph_optimize(h->pose_graph, poses16_in, n, edges, n_edges, max_iterations, band, poses16_out, result, trace, h->stream,
+                               h->ev0, h->ev1);
+  } catch (const std::exception& e) {
+    set_last_error(std::string("pose graph: host allocation failed: ") + e.what());
+    return LSR_ERR_HIP;
+  }
+}
+
 int lsr_nearest_neighbors(lsr_handle h, const float* T16, int32_t* idx, float* d2) {
   LSR_CHECK_HANDLE(h);
   if (!h->target || h->target->n == 0) return LSR_ERR_NO_TARGET;

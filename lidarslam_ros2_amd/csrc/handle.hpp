@@ -5,6 +5,7 @@
 #include "gicp.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
+#include "pose_graph.hpp"
 
 namespace lsr {
 // A deferred stream dependency (round 6): the group launches of a candidate set run on the FIRST member's stream; instead of making
@@ -89,6 +90,8 @@ struct lsr_handle_s {
   GicpWorkspace gicp_ws;
 
   lsr::DeskewState deskew;   // IMU queue and de-skew scratch (use_imu frontend path, csrc/deskew.hip)
+
+  lsr::PgWorkspace pose_graph;   // lsr_optimize_pose_graph (csrc/pose_graph.hip): device buffers, kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1): one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

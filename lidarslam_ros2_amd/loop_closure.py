@@ -3,10 +3,11 @@
 
 `SubMap` mirrors lidarslam_msgs/msg/SubMap (distance, pose, cloud); `LoopClosureParams` the node parameters
 searchLoop() reads (graph_based_slam_component.cpp:23-38, same names and defaults).  `search_loop` returns the
-`LoopEdge`s the reference would push into `loop_edges_` (accepted ones) plus the rejected evaluations; the pose
-graph optimisation that follows (doPoseAdjustment, g2o) is the caller's.  What the caller does with the optimiser's
-poses right afterwards — every submap moved by its new pose, the whole map put together
-(graph_based_slam_component.cpp:321-368) — is `map_array.MapArray.modified_map` (`Registration.assembleMap`).
+`LoopEdge`s the reference would push into `loop_edges_` (accepted ones) plus the rejected evaluations.  The pose
+graph optimisation that follows (doPoseAdjustment, graph_based_slam_component.cpp:267-319) is
+`map_array.MapArray.pose_adjustment` (`Registration.optimizePoseGraph`, pose_graph.py; no g2o), and what the caller
+does with the optimiser's poses right afterwards — every submap moved by its new pose, the whole map put together
+(:321-368) — is `map_array.MapArray.modified_map` (`Registration.assembleMap`).
 """
 from __future__ import annotations
 

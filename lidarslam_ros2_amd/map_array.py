@@ -15,8 +15,9 @@ from typing import List
 
 import numpy as np
 
+from . import _capi
 from .loop_closure import SubMap
-from .posemath import quaternion_from_matrix
+from .posemath import matrix_from_pose, quaternion_from_matrix
 from .registration import PC2_XYZI, _is_torch_cuda
 
 
@@ -66,6 +67,28 @@ class MapArray:
         """The map half of doPoseAdjustment (:321-368): every submap moved by the optimiser's estimate for it (4x4 fp64 each).
         records[first_record[i]:first_record[i + 1]] is modified_map_array.submaps[i].cloud (:343-351).  -> (records, first_record)."""
         return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
+
+    def stored_poses(self) -> np.ndarray:
+        """(n, 4, 4) fp64: the pose every stored SubMap message stands for (Eigen::fromMsg, graph_based_slam_component.cpp:279-281)."""
+        return np.stack([matrix_from_pose(s.position, s.orientation) for s in self.submaps])
+
+    def pose_adjustment(self, reg, loop_edges, num_adjacent: int = 5, max_iterations: int = 10, result=None):
+        """The optimiser half of doPoseAdjustment (:267-319): the stored poses as vertices (vertex 0 fixed), the odometry edges of
+        :289-303, one edge per accepted `LoopEdge` of `loop_edges` (what the reference keeps in loop_edges_; rejected ones are skipped),
+        optimize(max_iterations) on the device.  -> (n, 4, 4) fp64 poses for `modified_map`.  `result`: a list that receives the
+        pose_graph.PoseGraphResult.  The solve's band is min(num_adjacent, LSR_POSE_GRAPH_MAX_BAND = 8): with num_adjacent > 8 the
+        odometry edges longer than 8 count against the limit of 64 edges outside the band, which all but the shortest drives exceed —
+        the call then raises (invalid argument) and changes nothing."""
+        from . import pose_graph
+
+        poses = self.stored_poses()
+        edges = pose_graph.adjacent_edges(poses, num_adjacent)
+        edges += [(int(e.pair_id[0]), int(e.pair_id[1]), np.asarray(e.relative_pose, np.float64)) for e in loop_edges
+                  if getattr(e, "accepted", True)]
+        out, res = reg.optimizePoseGraph(poses, edges, max_iterations, min(int(num_adjacent), _capi.POSE_GRAPH_MAX_BAND))
+        if result is not None:
+            result.append(res)
+        return out
 
     def extend_published(self, reg):
         """publishMap for a frontend whose stored poses never change: only the submaps added since the last call are moved, appended to
