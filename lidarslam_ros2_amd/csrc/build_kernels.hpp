@@ -11,7 +11,7 @@ namespace {
 __global__ __launch_bounds__(256) void leaf_key_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                        const float* __restrict__ z, int n, float inv_leaf, int mb0, int mb1,
                                                        int mb2, int mul1, int mul2, unsigned int sentinel,
-                                                       unsigned int* __restrict__ key, int* __restrict__ val,
+                                                       unsigned int* __restrict__ key,
                                                        uint4* __restrict__ fill_a, size_t n_a, int* __restrict__ fill_b, size_t n_b,
                                                        int* __restrict__ zero_word) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -29,8 +29,7 @@ __global__ __launch_bounds__(256) void leaf_key_kernel(const float* __restrict__
     int i2 = (int)(floorf(pz * inv_leaf) - (float)mb2);
     k = (unsigned int)(i0 + i1 * mul1 + i2 * mul2);
   }
-  key[i] = k;
-  if (val) val[i] = i;   // (the hand-written sort numbers the values itself)
+  key[i] = k;   // (the sort numbers the values itself)
 }
 
 inline int bits_for(unsigned int max_key) {  // radix bits needed to order keys in [0, max_key]

@@ -204,83 +204,44 @@ int transform_to_strided(const DeviceCloud& src, const float* d_T16, void* d_out
 // ---- N1: pcl::VoxelGrid::filter (centroid per occupied leaf, output ordered by leaf index) -------------
 // scanmatcher/src/scanmatcher_component.cpp:324-328 (every scan, vg_size_for_input), :266-269, :443-447
 // (map side, vg_size_for_map), graph_based_slam/src/graph_based_slam_component.cpp:224-226.
-// Same key/sort machinery as K1; one thread per leaf sums its (few) points in ascending point order in FLOAT, as
+// Same key/sort machinery as K1; one thread per leaf (sorted_runs_centroids, lsd_sort.hip) sums its (few) points in ascending point order in FLOAT, as
 // pcl::CentroidPoint does (PCL's own order inside a leaf is whatever std::sort leaves: unspecified; ascending index is
 // the oracle's choice and this kernel's) — all fields, intensity included (downsample_all_data_).
-namespace {
-__global__ __launch_bounds__(256) void leaf_centroid_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                            const float* __restrict__ z, const float* __restrict__ w /*nullable*/,
-                                                            const int* __restrict__ order,
-                                                            const unsigned int* __restrict__ run_key, const int* __restrict__ run_off,
-                                                            const int* __restrict__ run_cnt, int n_runs, unsigned int sentinel,
-                                                            float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
-                                                            float* __restrict__ ow) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_runs) return;
-  if (run_key[r] == sentinel) return;  // the run of non-finite points (always last) is dropped
-  const int off = run_off[r], cnt = run_cnt[r];
-  // FLOAT accumulators, points in ascending index (stable sort): the very additions pcl::CentroidPoint performs
-  // (AccumulatorXYZ / AccumulatorIntensity are float), so the centroid is bit-identical to the CPU restatement
-  float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
-  for (int j = 0; j < cnt; j++) {
-    const int pi = order[off + j];
-    sx += x[pi]; sy += y[pi]; sz += z[pi];
-    if (w) sw += w[pi];
-  }
-  const float m = (float)cnt;
-  ox[r] = sx / m; oy[r] = sy / m; oz[r] = sz / m;
-  if (ow) ow[r] = w ? sw / m : 0.f;
-}
-}  // namespace
-
 int voxel_grid_filter(const DeviceCloud& cloud, float leaf, DeviceCloud& out, BuildScratch& sc, hipStream_t stream) {
   const int n = (int)cloud.n;
   out.n = 0;
   if (n == 0) return out.resize(0, cloud.has_i);
   int st;
-  // A/B switches, read once: LSR_VG_SORT=rocprim — the rocPRIM radix sort + run_length_encode + scan path of rounds 1-4;
-  // LSR_VG_DEVICE_DIMS=0 — always work out the grid dimensions on the host
-  static const bool use_rocprim = [] { const char* e = getenv("LSR_VG_SORT"); return e && e[0] == 'r'; }();
+  // A/B switch, read once: LSR_VG_DEVICE_DIMS=0 — always work out the grid dimensions on the host
   static const bool device_dims = [] { const char* e = getenv("LSR_VG_DEVICE_DIMS"); return !(e && e[0] == '0'); }();
   const float inv_leaf = 1.0f / leaf;
-  const size_t nrb = sorted_runs_blocks((size_t)n);
-  if ((st = sc.words.reserve(32 + 7 * (size_t)n + 2 * nrb + 16))) return st;
-  unsigned int* dims_dev = sc.words.p + 16;   // {sentinel, finite points, flags, key bits} of the device-side form
-  unsigned int* key_in = sc.words.p + 32;
-  unsigned int* key_out = key_in + n;
-  int* val_in = (int*)(key_out + n);
-  int* val_out = val_in + n;
-  unsigned int* run_key = (unsigned int*)(val_out + n);
-  int* run_cnt = (int*)(run_key + n);
-  int* run_off = run_cnt + n;
-  int* d_nruns = run_off + n;
-  int* block_heads = d_nruns + 8;
-  int* block_base = block_heads + nrb;
+  SortScratch s;
+  if ((st = sort_scratch_carve(sc, (size_t)n, false, &s))) return st;
+  unsigned int* dims_dev = sc.words.p + 16;   // {sentinel, finite points, flags, key bits} of the device-side form, in front of the ladder
+  const unsigned int* ks;
+  const int* vs;
 
   // ---- device-side dimensions: the pass that wrote `cloud` left its bounding-box records in device memory (pc2_ingest) and an earlier
   // call on this scratch says how many key bits such a cloud needs -> key (folds the records itself), sort, run heads and centroids are
   // enqueued back to back; the host waits ONCE, for {runs, finite points, flags}.  A cloud that needs more bits than planned (or whose
   // index space overflows) comes back flagged and takes the host-side form below, which also renews the hint.
-  if (!use_rocprim && device_dims && cloud.bbox_enqueued && !cloud.bbox_valid && sc.bbox_parts > 0 && sc.bbox_dev.p && sc.vg_bits_hint > 0 &&
+  if (device_dims && cloud.bbox_enqueued && !cloud.bbox_valid && sc.bbox_parts > 0 && sc.bbox_dev.p && sc.vg_bits_hint > 0 &&
       sc.vg_hint_leaf == leaf) {   // (an object that filters at two leaf sizes in turn — scans and keyframes — stays on the host form)
     const int planned_bits = sc.vg_bits_hint;
     LsdFirstHist fh;
     if ((st = lsd_first_hist_plan((size_t)n, planned_bits, sc.temp, &fh))) return st;
     if (fh.usable)   // the key kernel counts the first digit on the sort's own workgroups: the sort starts with its scatter
       hipLaunchKernelGGL(leaf_key_dims_hist_kernel, dim3(fh.nblk), dim3(256), (size_t)fh.C * 4, stream, cloud.x(), cloud.y(), cloud.z(), n,
-                         inv_leaf, sc.bbox_dev.p, sc.bbox_parts, planned_bits, key_in, dims_dev, fh.mask, fh.C, fh.hist, fh.row_pitch);
+                         inv_leaf, sc.bbox_dev.p, sc.bbox_parts, planned_bits, s.key_in, dims_dev, fh.mask, fh.C, fh.hist, fh.row_pitch);
     else
       hipLaunchKernelGGL(leaf_key_dims_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cloud.x(), cloud.y(), cloud.z(), n, inv_leaf,
-                         sc.bbox_dev.p, sc.bbox_parts, planned_bits, key_in, dims_dev);
-    bool in_b = false;
-    if ((st = sort_pairs_u32_lsd(key_in, key_out, nullptr, val_in, val_out, (size_t)n, planned_bits, sc.temp, stream, &in_b, fh.usable))) return st;
-    const unsigned int* ks = in_b ? key_out : key_in;
-    const int* vs = in_b ? val_out : val_in;
+                         sc.bbox_dev.p, sc.bbox_parts, planned_bits, s.key_in, dims_dev);
+    if ((st = sort_scratch_run(s, (size_t)n, planned_bits, sc.temp, stream, &ks, &vs, fh.usable))) return st;
     unsigned int token = 0;
-    if ((st = sorted_runs_begin(ks, (size_t)n, block_heads, block_base, sc, stream, &token, dims_dev))) return st;
+    if ((st = sorted_runs_begin(ks, (size_t)n, s.block_heads, s.block_base, sc, stream, &token, dims_dev))) return st;
     // the centroids do not wait for the count: the planes are laid out for n runs, the cloud shrinks to what was found
     if ((st = out.resize((size_t)n, cloud.has_i))) return st;
-    if ((st = sorted_runs_centroids(ks, vs, (size_t)n, block_base, 0u, cloud.x(), cloud.y(), cloud.z(), cloud.i(), out.x(), out.y(), out.z(),
+    if ((st = sorted_runs_centroids(ks, vs, (size_t)n, s.block_base, 0u, cloud.x(), cloud.y(), cloud.z(), cloud.i(), out.x(), out.y(), out.z(),
                                     out.i(), stream, dims_dev))) return st;
     int n_runs = 0;
     if ((st = sorted_runs_count(sc, stream, token, &n_runs))) return st;
@@ -322,35 +283,19 @@ int voxel_grid_filter(const DeviceCloud& cloud, float leaf, DeviceCloud& out, Bu
   sc.vg_bits_hint = bits_for(sentinel);
   sc.vg_hint_leaf = leaf;
   hipLaunchKernelGGL(leaf_key_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cloud.x(), cloud.y(), cloud.z(), n, inv_leaf,
-                     min_b[0], min_b[1], min_b[2], div_b[0], div_b[0] * div_b[1], sentinel, key_in, val_in, (uint4*)nullptr, (size_t)0,
+                     min_b[0], min_b[1], min_b[2], div_b[0], div_b[0] * div_b[1], sentinel, s.key_in, (uint4*)nullptr, (size_t)0,
                      (int*)nullptr, (size_t)0, (int*)nullptr);
-  if (!use_rocprim) {
-    // hand-written stable LSD sort (three passes for a 27-bit leaf index) + run heads + centroids: lsd_sort.hip
-    bool in_b = false;
-    if ((st = sort_pairs_u32_lsd(key_in, key_out, nullptr, val_in, val_out, (size_t)n, bits_for(sentinel), sc.temp, stream, &in_b))) return st;
-    const unsigned int* ks = in_b ? key_out : key_in;
-    const int* vs = in_b ? val_out : val_in;
-    unsigned int token = 0;
-    if ((st = sorted_runs_begin(ks, (size_t)n, block_heads, block_base, sc, stream, &token))) return st;
-    // the centroids do not wait for the count either (planes laid out for n runs; shrunk below)
-    if ((st = out.resize((size_t)n, cloud.has_i))) return st;
-    if ((st = sorted_runs_centroids(ks, vs, (size_t)n, block_base, sentinel, cloud.x(), cloud.y(), cloud.z(), cloud.i(), out.x(), out.y(), out.z(),
-                                    out.i(), stream))) return st;
-    int n_runs = 0;
-    if ((st = sorted_runs_count(sc, stream, token, &n_runs))) return st;   // host mailbox: no D2H copy, no stream sync
-    return out.shrink((size_t)(n_runs - ((n_finite < (unsigned int)n) ? 1 : 0)));     // minus the sentinel run
-  }
-  if ((st = sort_pairs_u32(key_in, key_out, val_in, val_out, n, bits_for(sentinel), sc.temp, stream))) return st;
-  if ((st = run_length_encode_u32(key_out, n, run_key, run_cnt, d_nruns, sc.temp, stream))) return st;
+  // hand-written stable LSD sort (three passes for a 27-bit leaf index) + run heads + centroids: lsd_sort.hip
+  if ((st = sort_scratch_run(s, (size_t)n, bits_for(sentinel), sc.temp, stream, &ks, &vs))) return st;
+  unsigned int token = 0;
+  if ((st = sorted_runs_begin(ks, (size_t)n, s.block_heads, s.block_base, sc, stream, &token))) return st;
+  // the centroids do not wait for the count either (planes laid out for n runs; shrunk below)
+  if ((st = out.resize((size_t)n, cloud.has_i))) return st;
+  if ((st = sorted_runs_centroids(ks, vs, (size_t)n, s.block_base, sentinel, cloud.x(), cloud.y(), cloud.z(), cloud.i(), out.x(), out.y(), out.z(),
+                                  out.i(), stream))) return st;
   int n_runs = 0;
-  if ((st = publish_device_int(d_nruns, sc, stream, &n_runs))) return st;   // host mailbox: no D2H copy, no stream sync
-  if ((st = exclusive_scan_i32(run_cnt, run_off, n_runs, sc.temp, stream))) return st;
-  const int n_out = n_runs - ((n_finite < (unsigned int)n) ? 1 : 0);  // minus the sentinel run
-  if ((st = out.resize(n_out, cloud.has_i))) return st;
-  hipLaunchKernelGGL(leaf_centroid_kernel, dim3((n_runs + 255) / 256), dim3(256), 0, stream, cloud.x(), cloud.y(), cloud.z(), cloud.i(),
-                     val_out, run_key, run_off, run_cnt, n_runs, sentinel, out.x(), out.y(), out.z(), out.i());
-  LSR_HIP(hipGetLastError());
-  return LSR_OK;
+  if ((st = sorted_runs_count(sc, stream, token, &n_runs))) return st;   // host mailbox: no D2H copy, no stream sync
+  return out.shrink((size_t)(n_runs - ((n_finite < (unsigned int)n) ? 1 : 0)));     // minus the sentinel run
 }
 
 // SoA planes -> strided xyz records (device to device)

@@ -3,7 +3,7 @@
 // index space is too large for one counting sort — built from the stages of the dense voxel-grid builder (grid_dense.hip): per
 // workgroup LDS histogram of the digit -> per digit exclusive scan over the workgroups -> stable scatter (which scans the digit
 // totals itself).
-// Three passes of 10 bits order a 28-bit leaf index (three launches each); rocPRIM's sort, which this replaces on these paths, spends a dozen
+// Three passes of 10 bits order a 28-bit leaf index (three launches each); the library merge sort this replaced on these paths spent a dozen
 // dependent launches of 5-10 us each on the same 147k keys (profiles/r04_rocprofv3_bench_stats.md: merge_sort_block_merge x 523).
 //
 // Stability does not lean on the order in which the LDS unit serves the lanes of one atomic instruction (the dense builder's
@@ -13,8 +13,8 @@
 // makes the second pass correct and what pcl::VoxelGrid's float centroid (points of a leaf summed in ascending index) needs.
 //
 // The tail of N1 lives here too: the heads of the runs of equal keys are counted per workgroup, scanned by one workgroup (which
-// also reports the number of runs to the host mailbox), and every head then sums its run — three launches instead of rocPRIM's
-// run_length_encode + exclusive_scan + a publishing launch.
+// also reports the number of runs to the host mailbox), and every head then sums its run — three launches instead of a library's
+// run-length encode + exclusive scan + a publishing launch.
 #include "handle.hpp"
 #include "sort.hpp"
 
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void rs_centroid_kernel(const unsigned int* __
   if (ow) ow[r] = w ? sw / m : 0.f;
 }
 
-// The runs as a table (what rocPRIM's run_length_encode + exclusive_scan gave the sort-based builders): run r in key order has
+// The runs as a table (what a run-length encode followed by an exclusive scan gives): run r in key order has
 // key run_key[r] and covers the sorted positions [run_off[r], run_off[r + 1]); run_off[number of runs] = n closes the table.
 __global__ __launch_bounds__(256) void rs_runs_table_kernel(const unsigned int* __restrict__ keys, int n, const int* __restrict__ block_base,
                                                             unsigned int* __restrict__ run_key, int* __restrict__ run_off) {
@@ -516,6 +516,33 @@ int sort_pairs_u32_lsd(unsigned int* key_a, unsigned int* key_b, int* val_a /*nu
   }
   LSR_HIP(hipGetLastError());
   return LSR_OK;
+}
+
+int sort_scratch_carve(BuildScratch& sc, size_t n, bool run_table, SortScratch* out) {
+  // pad[32] | key_in[n] | key_out[n] | val_in[n] | val_out[n] | block_heads[nb] | block_base[nb] | run_key[n+1] | run_off[n+1] | nruns[16]
+  const size_t nb = sorted_runs_blocks(n);
+  int st = sc.words.reserve(32 + 4 * n + 2 * nb + (run_table ? 2 * (n + 1) + 16 : 0));
+  if (st) return st;
+  SortScratch& s = *out;
+  s.key_in = sc.words.p + 32;
+  s.key_out = s.key_in + n;
+  s.val_in = (int*)(s.key_out + n);
+  s.val_out = s.val_in + n;
+  s.block_heads = s.val_out + n;
+  s.block_base = s.block_heads + nb;
+  s.run_key = run_table ? (unsigned int*)(s.block_base + nb) : nullptr;
+  s.run_off = run_table ? (int*)(s.run_key + n + 1) : nullptr;
+  s.nruns = run_table ? s.run_off + n + 1 : nullptr;
+  return LSR_OK;
+}
+
+int sort_scratch_run(const SortScratch& s, size_t n, int end_bit, DevBuf<char>& temp, hipStream_t stream, const unsigned int** keys,
+                     const int** order, bool first_hist_done) {
+  bool in_b = false;
+  int st = sort_pairs_u32_lsd(s.key_in, s.key_out, nullptr, s.val_in, s.val_out, n, end_bit, temp, stream, &in_b, first_hist_done);
+  *keys = in_b ? s.key_out : s.key_in;
+  *order = in_b ? s.val_out : s.val_in;
+  return st;
 }
 
 int sorted_runs_begin(const unsigned int* keys_sorted, size_t n, int* block_heads, int* block_base, BuildScratch& sc, hipStream_t stream,

@@ -223,9 +223,6 @@ void ndt_fill_diag_state(NdtState& st, const double* p6, const float* T16, int c
 // Host helper: default state constants for an align.
 void ndt_fill_align_constants(NdtState& st, const NdtParamsHost& prm, int n_points);
 
-// One device int to the host through the build mailbox (a 1-thread launch + one polled word instead of a device-to-host
-// copy and a stream synchronisation).  Defined in grid_dense.hip.
-int publish_device_int(const int* d_value, BuildScratch& sc, hipStream_t stream, int* out);
 // N4: PointCloud2 payload (float32 fields at byte offsets ox/oy/oz/oi inside point_step records; oi < 0: no intensity)
 // <-> SoA planes, device to device.
 int pc2_write(const DeviceCloud& in, void* d_data, int step, int ox, int oy, int oz, int oi, hipStream_t stream);

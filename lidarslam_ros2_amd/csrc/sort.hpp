@@ -2,14 +2,6 @@
 #include "common.hpp"
 
 namespace lsr {
-// Stable LSD radix sort of (key, value) pairs on bits [0, end_bit).
-int sort_pairs_u32(const uint32_t* keys_in, uint32_t* keys_out, const int* vals_in, int* vals_out, size_t n,
-                   int end_bit, DevBuf<char>& temp, hipStream_t stream);
-// Runs of equal keys: unique_out[r], counts_out[r], *num_runs_out (device int).
-int run_length_encode_u32(const uint32_t* keys_sorted, size_t n, uint32_t* unique_out, int* counts_out,
-                          int* num_runs_out, DevBuf<char>& temp, hipStream_t stream);
-int exclusive_scan_i32(const int* in, int* out, size_t n, DevBuf<char>& temp, hipStream_t stream);
-
 // ---- hand-written stable LSD radix sort + run finder (lsd_sort.hip) -------------------------------------------------------
 // Sorts n pairs on key bits [0, end_bit) in ceil(end_bit / 11) passes, ping-ponging between (key_a, val_a) and (key_b, val_b);
 // val_a == nullptr: the values are 0..n-1 (no iota pass), val_a_buf then serves as the "a" side from the second pass on.
@@ -17,6 +9,20 @@ int exclusive_scan_i32(const int* in, int* out, size_t n, DevBuf<char>& temp, hi
 struct BuildScratch;
 int sort_pairs_u32_lsd(unsigned int* key_a, unsigned int* key_b, int* val_a, int* val_a_buf, int* val_b, size_t n, int end_bit,
                        DevBuf<char>& temp, hipStream_t stream, bool* result_in_b, bool first_hist_done = false);
+// The scratch of a sort-based builder, carved out of sc.words for n keys: both sides of the sort's ping-pong and the run heads' block
+// tables; with a run table also run_key / run_off (n + 1 entries each) and 16 ints, the first of them for the run count in device
+// memory (null otherwise).  The ladder starts 32 words into sc.words; the words in front of it are the caller's.
+struct SortScratch {
+  unsigned int *key_in, *key_out;
+  int *val_in, *val_out;
+  int *block_heads, *block_base;
+  unsigned int* run_key;
+  int *run_off, *nruns;
+};
+int sort_scratch_carve(BuildScratch& sc, size_t n, bool run_table, SortScratch* out);
+// Sorts s.key_in with the values 0..n-1 on bits [0, end_bit): *keys / *order say where the sorted keys and the order ended up.
+int sort_scratch_run(const SortScratch& s, size_t n, int end_bit, DevBuf<char>& temp, hipStream_t stream, const unsigned int** keys,
+                     const int** order, bool first_hist_done = false);
 // The first pass's histogram table as that call will lay it out in temp: digit-major uint16 rows hist[digit * row_pitch + workgroup],
 // workgroup = 2048 consecutive keys (key i of workgroup b: b * 2048 + i), digit = key & mask.  A kernel that produces the keys may fill
 // it and pass first_hist_done = true (only when `usable`).

@@ -47,8 +47,8 @@ stats target python $REPO/tools/target_probe.py
 # kernel timeline of a whole share (tools/share_probe.py, tools/timeline.py)
 (for F in 0 24; do FIRST=$F timeout 300 python tools/share_probe.py 2>&1 | tail -1; done) > $P/${TAG}_cfg4_share.txt
 (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tr_share && FIRST=24 MODE=share REPS=3 timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tr_share -o t -- python $REPO/tools/share_probe.py > /dev/null 2>&1; python $REPO/tools/timeline.py /tmp/tr_share 300 2000 | tail -75 >> $P/${TAG}_cfg4_share.txt 2>&1)
-# 3d. N1: the frontend's source preprocessing (hand-written LSD sort) against the rocPRIM path it replaces
-(for v in lsd rocprim; do echo "[LSR_VG_SORT=$v]"; LSR_VG_SORT=$v timeout 300 python tools/preprocess_probe.py 2>&1 | tail -1; done) > $P/${TAG}_n1_preprocess.txt
+# 3d. N1: the frontend's source preprocessing (hand-written LSD sort)
+(timeout 300 python tools/preprocess_probe.py 2>&1 | tail -1) > $P/${TAG}_n1_preprocess.txt
 stats n1 python $REPO/tools/preprocess_probe.py
 # 3e. ONE frontend scan at the reference's settings (payload in HBM -> lsr_set_input_source_pc2 -> lsr_align): host-clock medians and the
 # kernel timeline of a scan (tools/frontend_scan_probe.py, tools/timeline.py)
