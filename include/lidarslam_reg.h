@@ -68,6 +68,11 @@ typedef enum lsr_key {
   LSR_GICP_EPSILON = 7,               /* GICP gicp_epsilon_ (1e-3) */
   LSR_MAP_ASSEMBLY_MS = 8,            /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the launches of the last
                                          lsr_assemble_map on this object (the kernel alone: staging copies are outside the bracket); else 0 */
+  LSR_POSE_GRAPH_BAND_SOLVE_MS = 9,   /* read-only (lsr_get_f64), the next two likewise: with LSR_PROFILE = 1, three stages of the last
+                                         lsr_optimize_pose_graph / _long on this object, each between hipEvents and summed over its trials
+                                         [ms]: the right-hand sides and the 1 + 6L band solves; */
+  LSR_POSE_GRAPH_DENSE_MS = 10,       /* the dense part (C = I + U B^-1 U^T formed, factored and solved); */
+  LSR_POSE_GRAPH_COMBINE_MS = 11,     /* the row combine x = B^-1 b - B^-1 U^T z.  Else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -480,6 +485,7 @@ int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, c
 #define LSR_POSE_GRAPH_MAX_VERTICES 8192
 #define LSR_POSE_GRAPH_MAX_BAND 8
 #define LSR_POSE_GRAPH_MAX_OFFBAND_EDGES 64
+#define LSR_POSE_GRAPH_LONG_MAX_OFFBAND_EDGES 1024
 typedef struct lsr_pose_edge {
   int32_t from, to;             /* EdgeSE3::vertices()[0], [1] */
   double measurement[16];       /* from^-1 * to, column-major 4x4 fp64: the layout of lsr_loop_edge.relative_pose */
@@ -529,6 +535,20 @@ int lsr_pose_graph_edges(const double* poses16, int n, int num_adjacent, lsr_pos
 int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
                             const lsr_pose_graph_params* params /* nullable */, double* poses16_out, lsr_pose_graph_result* result,
                             lsr_pose_graph_trace* trace /* nullable */);
+/* The same call for a drive of ordinary length: the reference keeps every accepted loop edge for the life of the node (loop_edges_ only
+ * grows, :247; all of them are added, :308-315), so a revisit of two minutes passes LSR_POSE_GRAPH_MAX_OFFBAND_EDGES.  Same nine
+ * parameters, same contract — outputs untouched on every error, n == 1 or n_edges == 0 served trivially — with
+ * LSR_POSE_GRAPH_LONG_MAX_OFFBAND_EDGES in the place of LSR_POSE_GRAPH_MAX_OFFBAND_EDGES.  With at most LSR_POSE_GRAPH_MAX_OFFBAND_EDGES
+ * edges outside the band it runs what lsr_optimize_pose_graph runs and returns the same bits.  Above, the dense part of the Woodbury
+ * split (6L x 6L, L the edges outside the band) is a blocked fp64 Cholesky over many workgroups and the rows are combined a wave per
+ * row: the same system, another summation order (DESIGN.md 4 "Pose-graph optimisation" has the measured differences), bit-identical
+ * from call to call.
+ * Workspace, reserved on the object when such a graph arrives and kept: the right-hand sides W, 6(n - 1) x (1 + 6L) doubles — 2.4 GB at
+ * 8192 vertices and 1024 edges outside the band, 0.6 GB at 2048 vertices — and the dense matrix C, 36 L^2 doubles, 302 MB at 1024
+ * edges.  A reservation that fails is LSR_ERR_HIP with the outputs untouched. */
+int lsr_optimize_pose_graph_long(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
+                                 const lsr_pose_graph_params* params /* nullable */, double* poses16_out, lsr_pose_graph_result* result,
+                                 lsr_pose_graph_trace* trace /* nullable */);
 
 /* ---- inspection (parity tests / profiling; not used by the ROS nodes) ------------------- */
 /* NDT voxel grid: info[0..2]=min_b, [3..5]=max_b, [6]=#leaves (any point count), [7]=#leaves usable (n>=6, valid cov) */

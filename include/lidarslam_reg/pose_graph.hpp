@@ -1,4 +1,4 @@
-// lidarslam_reg/pose_graph.hpp — header-only helper over lsr_pose_graph_edges / lsr_optimize_pose_graph (lidarslam_reg.h): the
+// lidarslam_reg/pose_graph.hpp — header-only helper over lsr_pose_graph_edges / lsr_optimize_pose_graph_long (lidarslam_reg.h): the
 // optimiser half of doPoseAdjustment on the device, without g2o.
 //
 //   graph_based_slam/src/graph_based_slam_component.cpp:267-319   g2o::SparseOptimizer, VertexSE3 / EdgeSE3, optimize(10)
@@ -64,7 +64,8 @@ inline bool adjacentPoseEdges(const std::vector<Pose>& poses, int num_adjacent, 
 // optimizer.initializeOptimization(); optimizer.optimize(max_iterations) (:317-318): `poses` are the vertices' estimates (vertex 0
 // fixed), `edges` the odometry edges followed by the loop edges; `optimized` receives vertex->estimate() of every vertex — what
 // lidarslam_reg::assembleMap (map_assembly.hpp) takes as poses.  Reports like the registration adapter does (stderr, false) and leaves
-// `optimized` as it was on failure.
+// `optimized` as it was on failure.  Through lsr_optimize_pose_graph_long: up to LSR_POSE_GRAPH_LONG_MAX_OFFBAND_EDGES loop edges, so
+// loop_edges_ may keep growing over a drive (:247); within LSR_POSE_GRAPH_MAX_OFFBAND_EDGES the bits are lsr_optimize_pose_graph's.
 template <typename Pose>
 inline bool optimizePoseGraph(lsr_handle h, const std::vector<Pose>& poses, const std::vector<lsr_pose_edge>& edges,
                               std::vector<Pose>& optimized, lsr_pose_graph_result* result = nullptr, int max_iterations = 10, int band = 5,
@@ -74,8 +75,8 @@ inline bool optimizePoseGraph(lsr_handle h, const std::vector<Pose>& poses, cons
   std::vector<lsr_pose_graph_trace> tr((size_t)(max_iterations > 0 ? max_iterations : 0));
   lsr_pose_graph_params params = {max_iterations, band};
   lsr_pose_graph_result res;
-  const int st = lsr_optimize_pose_graph(h, P.data(), (int)poses.size(), edges.data(), (int)edges.size(), &params, out.data(), &res,
-                                         tr.empty() ? nullptr : tr.data());
+  const int st = lsr_optimize_pose_graph_long(h, P.data(), (int)poses.size(), edges.data(), (int)edges.size(), &params, out.data(),
+                                              &res, tr.empty() ? nullptr : tr.data());
   if (st != LSR_OK) {
     std::fprintf(stderr, "[lidarslam_reg::optimizePoseGraph] %s: %s\n", lsr_status_string(st), lsr_last_error());
     return false;

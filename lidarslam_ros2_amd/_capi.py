@@ -15,10 +15,12 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("LSR_LIB_NAME", "liblidarslam_reg.
 # enums (mirror include/lidarslam_reg.h)
 OK = 0
 POSE_GRAPH_MAX_VERTICES, POSE_GRAPH_MAX_BAND, POSE_GRAPH_MAX_OFFBAND_EDGES = 8192, 8, 64
+POSE_GRAPH_LONG_MAX_OFFBAND_EDGES = 1024
 METHOD_NDT, METHOD_GICP = 0, 1
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
 (RESOLUTION, TRANSFORMATION_EPSILON, STEP_SIZE, OUTLIER_RATIO, MAX_CORRESPONDENCE_DISTANCE, ROTATION_EPSILON,
- EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON, MAP_ASSEMBLY_MS) = range(9)
+ EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON, MAP_ASSEMBLY_MS, POSE_GRAPH_BAND_SOLVE_MS, POSE_GRAPH_DENSE_MS,
+ POSE_GRAPH_COMBINE_MS) = range(12)
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
  HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED,
  MAP_ASSEMBLY_FORM) = range(32, 50)
@@ -35,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
     "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
-    "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph",
+    "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long",
 ]
 
 
@@ -158,8 +160,9 @@ def load() -> C.CDLL:
     L.lsr_assemble_map.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, vp, C.c_size_t, C.POINTER(Pc2Layout),
                                    C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.lsr_pose_graph_edges.argtypes = [dp, C.c_int, C.c_int, C.POINTER(PoseEdge), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lsr_optimize_pose_graph.argtypes = [vp, dp, C.c_int, C.POINTER(PoseEdge), C.c_int, C.POINTER(PoseGraphParams), dp,
-                                          C.POINTER(PoseGraphResult), C.POINTER(PoseGraphTrace)]
+    for name in ("lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long"):
+        getattr(L, name).argtypes = [vp, dp, C.c_int, C.POINTER(PoseEdge), C.c_int, C.POINTER(PoseGraphParams), dp,
+                                     C.POINTER(PoseGraphResult), C.POINTER(PoseGraphTrace)]
     L.lsr_ndt_grid_info.argtypes = [vp, ip]
     L.lsr_ndt_grid_dump.argtypes = [vp, ip, ip, dp, dp]
     L.lsr_ndt_grid_centroids.argtypes = [vp, fp]

@@ -920,6 +920,9 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_EUCLIDEAN_FITNESS_EPSILON: *v = h->euclidean_fitness_eps; return LSR_OK;
     case LSR_GICP_EPSILON: *v = h->gicp.gicp_eps; return LSR_OK;
     case LSR_MAP_ASSEMBLY_MS: *v = h->map_ms; return LSR_OK;
+    case LSR_POSE_GRAPH_BAND_SOLVE_MS: *v = h->pose_graph.stage_ms[0]; return LSR_OK;
+    case LSR_POSE_GRAPH_DENSE_MS: *v = h->pose_graph.stage_ms[1]; return LSR_OK;
+    case LSR_POSE_GRAPH_COMBINE_MS: *v = h->pose_graph.stage_ms[2]; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -2012,9 +2015,11 @@ int lsr_pose_graph_edges(const double* poses16, int n, int num_adjacent, lsr_pos
   return pose_graph_adjacent_edges(poses16, n, num_adjacent, out, capacity, n_out);   // allocates nothing
 }
 
-int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
-                            const lsr_pose_graph_params* params, double* poses16_out, lsr_pose_graph_result* result,
-                            lsr_pose_graph_trace* trace) {
+// both pose-graph entries: the arguments checked against `max_offband` edges outside the band (named `limit_name` in the refusal), the
+// trivial graphs served, then the optimiser
+static int optimize_pose_graph_checked(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
+                                       const lsr_pose_graph_params* params, double* poses16_out, lsr_pose_graph_result* result,
+                                       lsr_pose_graph_trace* trace, int max_offband, const char* limit_name) {
   LSR_CHECK_HANDLE(h);
   if (!poses16_in || !poses16_out || !result || n < 1 || n_edges < 0 || (n_edges > 0 && !edges)) {
     set_last_error("bad argument");
@@ -2034,8 +2039,8 @@ int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const
     }
     if (a != 0 && b != 0 && std::abs(a - b) > band) off_band++;
   }
-  if (off_band > PG_MAX_OFFBAND) {
-    set_last_error("pose graph: more than LSR_POSE_GRAPH_MAX_OFFBAND_EDGES edges outside the band");
+  if (off_band > max_offband) {
+    set_last_error(std::string("pose graph: more than ") + limit_name + " edges outside the band");
     return LSR_ERR_INVALID_ARGUMENT;
   }
   if (n == 1 || n_edges == 0) {
@@ -2045,12 +2050,27 @@ int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const
   }
   // the host side of the graph lives in std::vectors (up to 2^20 edges): nothing they throw crosses the C ABI
   try {
-    return pose_graph_optimize(h->pose_graph, poses16_in, n, edges, n_edges, max_iterations, band, poses16_out, result, trace, h->stream,
-                               h->ev0, h->ev1);
+    h->pose_graph.profile = h->profile != 0;
+    return pose_graph_optimize(h->pose_graph, poses16_in, n, edges, n_edges, max_iterations, band, max_offband, poses16_out, result, trace,
+                               h->stream, h->ev0, h->ev1);
   } catch (const std::exception& e) {
     set_last_error(std::string("pose graph: host allocation failed: ") + e.what());
     return LSR_ERR_HIP;
   }
+}
+
+int lsr_optimize_pose_graph(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
+                            const lsr_pose_graph_params* params, double* poses16_out, lsr_pose_graph_result* result,
+                            lsr_pose_graph_trace* trace) {
+  return optimize_pose_graph_checked(h, poses16_in, n, edges, n_edges, params, poses16_out, result, trace, PG_MAX_OFFBAND,
+                                     "LSR_POSE_GRAPH_MAX_OFFBAND_EDGES");
+}
+
+int lsr_optimize_pose_graph_long(lsr_handle h, const double* poses16_in, int n, const lsr_pose_edge* edges, int n_edges,
+                                 const lsr_pose_graph_params* params, double* poses16_out, lsr_pose_graph_result* result,
+                                 lsr_pose_graph_trace* trace) {
+  return optimize_pose_graph_checked(h, poses16_in, n, edges, n_edges, params, poses16_out, result, trace, PG_LONG_MAX_OFFBAND,
+                                     "LSR_POSE_GRAPH_LONG_MAX_OFFBAND_EDGES");
 }
 
 int lsr_nearest_neighbors(lsr_handle h, const float* T16, int32_t* idx, float* d2) {

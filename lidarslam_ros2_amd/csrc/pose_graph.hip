@@ -12,6 +12,8 @@
 //                     pg_fill_rhs, pg_band_solve (1 + 6L independent banded solves, one lane each)
 //                     pg_small_system, pg_dense_solve (C = I + U B^-1 U^T, 6L x 6L, Cholesky, z = C^-1 U B^-1 b)
 //                     pg_combine (x = B^-1 b - B^-1 U^T z), pg_update (X' = X (+) x), pg_error, pg_reduce_trial (chi2(X'), scale)
+//                     With more than LSR_POSE_GRAPH_MAX_OFFBAND_EDGES slots of U (lsr_optimize_pose_graph_long) pg_dense_solve and
+//                     pg_combine give way to the blocked Cholesky and the wave-per-row combine of csrc/pose_graph_dense.hip.
 // Hang safety: every loop below runs to a vertex, edge, band, column or slot count; no workgroup waits for another; a pivot that is
 // not positive and finite sets PgScalars::fail and the kernel returns; the kernels behind it return at once.
 #include <algorithm>
@@ -393,6 +395,19 @@ __global__ __launch_bounds__(PG_WG) void pg_update(const PgPose* __restrict__ X,
 
 inline int blocks(size_t n, int wg = PG_WG) { return (int)((n + wg - 1) / wg); }
 
+// the four events that bracket the three profiled stages of a trial (LSR_PROFILE)
+struct StageEvents {
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  int create() {
+    for (auto& e : ev) LSR_HIP(hipEventCreate(&e));
+    return LSR_OK;
+  }
+  ~StageEvents() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 }  // namespace
 
 int pose_graph_adjacent_edges(const double* poses16, int n, int num_adjacent, lsr_pose_edge* out, size_t capacity, size_t* n_out) {
@@ -425,8 +440,8 @@ int pose_graph_adjacent_edges(const double* poses16, int n, int num_adjacent, ls
 }
 
 int pose_graph_optimize(PgWorkspace& ws, const double* poses16_in, int n_vertices, const lsr_pose_edge* edges, int n_edges, int max_iterations,
-                        int band, double* poses16_out, lsr_pose_graph_result* result, lsr_pose_graph_trace* trace, hipStream_t stream,
-                        hipEvent_t ev0, hipEvent_t ev1) {
+                        int band, int max_offband, double* poses16_out, lsr_pose_graph_result* result, lsr_pose_graph_trace* trace,
+                        hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
   const int N = n_vertices, E = n_edges;
   const int n = 6 * (N - 1), hw = 6 * band + 5, ld = hw + 1;
 
@@ -452,7 +467,8 @@ int pose_graph_optimize(PgWorkspace& ws, const double* poses16_in, int n_vertice
     for (int k = 0; k < E; k++) { inc_edge[(size_t)fill[(size_t)he[(size_t)k].from]++] = k; inc_edge[(size_t)fill[(size_t)he[(size_t)k].to]++] = k; }
   }
   const int L = (int)off_edge.size(), m = 6 * L, ldw = 1 + m;
-  if (L > PG_MAX_OFFBAND) { set_last_error("pose graph: more off-band edges than LSR_POSE_GRAPH_MAX_OFFBAND_EDGES"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (L > max_offband) { set_last_error("pose graph: more off-band edges than the entry point's limit"); return LSR_ERR_INVALID_ARGUMENT; }
+  const bool blocked = L > PG_MAX_OFFBAND;   // the dense part by tiles over many workgroups (pose_graph_dense.hip)
 
   int st;
   if ((st = ws.X.reserve(N)) || (st = ws.Xt.reserve(N)) || (st = ws.edges.reserve(E)) || (st = ws.inc_start.reserve((size_t)N + 1)) ||
@@ -460,7 +476,7 @@ int pose_graph_optimize(PgWorkspace& ws, const double* poses16_in, int n_vertice
       (st = ws.Jf.reserve(36 * (size_t)E)) || (st = ws.Jt.reserve(36 * (size_t)E)) || (st = ws.ete.reserve(E)) ||
       (st = ws.AB.reserve((size_t)n * ld)) || (st = ws.LB.reserve((size_t)n * ld)) || (st = ws.b.reserve(n)) || (st = ws.diag.reserve(n)) ||
       (st = ws.x.reserve(n)) || (st = ws.W.reserve((size_t)n * ldw)) || (st = ws.C.reserve(std::max((size_t)m * m, (size_t)1))) ||
-      (st = ws.g.reserve(std::max(m, 1))) || (st = ws.d_sc.reserve(1)) || (st = ws.h_sc.reserve(1)) ||
+      (st = ws.g.reserve(std::max(m, 1))) || (blocked && (st = ws.z.reserve(m))) || (st = ws.d_sc.reserve(1)) || (st = ws.h_sc.reserve(1)) ||
       (st = ws.h_out.reserve(12 * (size_t)N)))
     return st;
   // uploads through one pinned staging buffer: poses | edges | inc_start | inc_edge | off_edge
@@ -491,6 +507,15 @@ int pose_graph_optimize(PgWorkspace& ws, const double* poses16_in, int n_vertice
     return LSR_OK;
   };
   const size_t factor_lds = sizeof(double) * (size_t)ld * ld, solve_lds = sizeof(double) * (size_t)ld * 64;
+  // LSR_PROFILE: three stages of every trial between events, read after the trial's own synchronisation
+  StageEvents sev;
+  const bool staged = ws.profile;
+  ws.stage_ms[0] = ws.stage_ms[1] = ws.stage_ms[2] = 0.0;
+  if (staged && (st = sev.create())) return st;
+  auto mark = [&](int i) -> int {
+    if (staged) LSR_HIP(hipEventRecord(sev.ev[i], stream));
+    return LSR_OK;
+  };
 
   lsr_pose_graph_result R;
   std::memset(&R, 0, sizeof(R));
@@ -514,20 +539,32 @@ int pose_graph_optimize(PgWorkspace& ws, const double* poses16_in, int n_vertice
     double rho = 0.0;
     do {
       hipLaunchKernelGGL(pg_band_factor, dim3(1), dim3(PG_WG), factor_lds, stream, ws.AB.p, lambda, n, hw, ws.LB.p, sc);
+      if ((st = mark(0))) return st;
       hipLaunchKernelGGL(pg_fill_rhs, dim3(blocks((size_t)n * ldw)), dim3(PG_WG), 0, stream, ws.edges.p, ws.off_edge.p, ws.Jf.p, ws.Jt.p,
                          ws.b.p, n, ldw, ws.W.p);
       hipLaunchKernelGGL(pg_band_solve, dim3(blocks(ldw, 64)), dim3(64), solve_lds, stream, ws.LB.p, n, hw, ws.W.p, ldw, ldw, sc);
+      if ((st = mark(1))) return st;
       if (m > 0) {
         hipLaunchKernelGGL(pg_small_system, dim3(blocks((size_t)m * (m + 1))), dim3(PG_WG), 0, stream, ws.edges.p, ws.off_edge.p, ws.Jf.p,
                            ws.Jt.p, ws.W.p, ldw, m, ws.C.p, ws.g.p, sc);
-        hipLaunchKernelGGL(pg_dense_solve, dim3(1), dim3(PG_WG), 0, stream, ws.C.p, ws.g.p, m, sc);
+        if (blocked) pose_graph_dense_solve(ws.C.p, ws.g.p, ws.z.p, m, sc, stream);
+        else hipLaunchKernelGGL(pg_dense_solve, dim3(1), dim3(PG_WG), 0, stream, ws.C.p, ws.g.p, m, sc);
       }
-      hipLaunchKernelGGL(pg_combine, dim3(blocks(n)), dim3(PG_WG), 0, stream, ws.W.p, ldw, m, ws.g.p, n, ws.x.p, sc);
+      if ((st = mark(2))) return st;
+      if (blocked) pose_graph_combine_rows(ws.W.p, ldw, m, ws.z.p, n, ws.x.p, sc, stream);
+      else hipLaunchKernelGGL(pg_combine, dim3(blocks(n)), dim3(PG_WG), 0, stream, ws.W.p, ldw, m, ws.g.p, n, ws.x.p, sc);
+      if ((st = mark(3))) return st;
       hipLaunchKernelGGL(pg_update, dim3(blocks(N)), dim3(PG_WG), 0, stream, X, ws.x.p, N, Xt, sc);
       hipLaunchKernelGGL(pg_error, dim3(blocks(E)), dim3(PG_WG), 0, stream, Xt, ws.edges.p, E, ws.ete.p);
       hipLaunchKernelGGL(pg_reduce_trial, dim3(1), dim3(PG_WG), 0, stream, ws.ete.p, E, ws.x.p, ws.b.p, n, lambda, sc);
       LSR_HIP(hipGetLastError());
       if ((st = read_scalars())) return st;
+      if (staged)
+        for (int i = 0; i < 3; i++) {
+          float part = 0.f;
+          LSR_HIP(hipEventElapsedTime(&part, sev.ev[i], sev.ev[i + 1]));
+          ws.stage_ms[i] += part;
+        }
       // a failed factorisation counts as a trial whose chi2 is the largest double and whose step is zero (g2o: tmp = max)
       const bool failed = ws.h_sc.p->fail != 0;
       const double tmp = failed ? DBL_MAX : ws.h_sc.p->trial_chi2;

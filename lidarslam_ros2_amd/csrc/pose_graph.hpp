@@ -7,7 +7,8 @@ namespace lsr {
 
 constexpr int PG_MAX_VERTICES = LSR_POSE_GRAPH_MAX_VERTICES;
 constexpr int PG_MAX_BAND = LSR_POSE_GRAPH_MAX_BAND;
-constexpr int PG_MAX_OFFBAND = LSR_POSE_GRAPH_MAX_OFFBAND_EDGES;
+constexpr int PG_MAX_OFFBAND = LSR_POSE_GRAPH_MAX_OFFBAND_EDGES;             // above it the dense part is blocked (pose_graph_dense.hip)
+constexpr int PG_LONG_MAX_OFFBAND = LSR_POSE_GRAPH_LONG_MAX_OFFBAND_EDGES;
 constexpr int PG_MAX_EDGES = 1 << 20;
 constexpr int PG_MAX_TRIALS = 10;   // g2o's maxTrialsAfterFailure
 
@@ -36,6 +37,9 @@ struct PgWorkspace {
   DevBuf<double> b, diag, x;       // b = -sum J^T e; the diagonal of the whole H; the increment
   DevBuf<double> W;                // [n][1 + 6L]: column 0 b -> B^-1 b, the others U^T -> B^-1 U^T
   DevBuf<double> C, g;             // I + U B^-1 U^T and U B^-1 b -> z
+  DevBuf<double> z;                // the blocked path (more than PG_MAX_OFFBAND slots) keeps y in g and writes z here
+  bool profile = false;            // LSR_PROFILE: three stages of every trial are bracketed with events ...
+  double stage_ms[3] = {0, 0, 0};  // ... and summed over the call: band solve (right-hand sides included), dense part, row combine
   DevBuf<PgScalars> d_sc;
   PinBuf<PgScalars> h_sc;
   PinBuf<unsigned char> h_up;      // staging of the uploads
@@ -44,9 +48,17 @@ struct PgWorkspace {
 
 // The whole of optimizer.optimize(max_iterations) (graph_based_slam_component.cpp:317-318).  Arguments are checked by the caller.
 // A host loop drives it: per linearisation and per trial it reads PgScalars back (one small copy) and decides accept / reject.
+// max_offband: the caller's limit on the slots of U.  Up to PG_MAX_OFFBAND of them the dense part is pg_dense_solve and the rows are
+// combined by pg_combine; above, pose_graph_dense_solve and pose_graph_combine_rows.
 int pose_graph_optimize(PgWorkspace& ws, const double* poses16_in, int n_vertices, const lsr_pose_edge* edges, int n_edges, int max_iterations,
-                        int band, double* poses16_out, lsr_pose_graph_result* result, lsr_pose_graph_trace* trace, hipStream_t stream,
-                        hipEvent_t ev0, hipEvent_t ev1);
+                        int band, int max_offband, double* poses16_out, lsr_pose_graph_result* result, lsr_pose_graph_trace* trace,
+                        hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
+
+// csrc/pose_graph_dense.hip.  C (m x m, row-major, lower triangle read) = L L^T in place by tiles, g -> y (L y = g) on the way, then
+// L^T z = y into z: 3 ceil(m / 64) + ceil(m / 64) launches on `stream`, none of them waiting for another workgroup.
+void pose_graph_dense_solve(double* C, double* g, double* z, int m, PgScalars* sc, hipStream_t stream);
+// x[row] = W[row][0] - sum_c W[row][1 + c] z[c], a wave per row
+void pose_graph_combine_rows(const double* W, int ldw, int m, const double* z, int n, double* x, const PgScalars* sc, hipStream_t stream);
 
 // the odometry edges of graph_based_slam_component.cpp:289-303 (host only)
 int pose_graph_adjacent_edges(const double* poses16, int n, int num_adjacent, lsr_pose_edge* out, size_t capacity, size_t* n_out);

@@ -77,8 +77,9 @@ class MapArray:
         :289-303, one edge per accepted `LoopEdge` of `loop_edges` (what the reference keeps in loop_edges_; rejected ones are skipped),
         optimize(max_iterations) on the device.  -> (n, 4, 4) fp64 poses for `modified_map`.  `result`: a list that receives the
         pose_graph.PoseGraphResult.  The solve's band is min(num_adjacent, LSR_POSE_GRAPH_MAX_BAND = 8): with num_adjacent > 8 the
-        odometry edges longer than 8 count against the limit of 64 edges outside the band, which all but the shortest drives exceed —
-        the call then raises (invalid argument) and changes nothing."""
+        odometry edges longer than 8 count as edges outside the band, like every loop edge.  Up to LSR_POSE_GRAPH_LONG_MAX_OFFBAND_EDGES
+        = 1024 of those are served (lsr_optimize_pose_graph_long: every loop edge a node has accepted over a few laps; past 64 the dense
+        part of the solve is a blocked Cholesky); beyond that the call raises (invalid argument) and changes nothing."""
         from . import pose_graph
 
         poses = self.stored_poses()

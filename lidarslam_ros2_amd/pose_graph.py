@@ -1,6 +1,7 @@
 """Pose-graph optimisation: the optimiser half of GraphBasedSlamComponent::doPoseAdjustment
-(graph_based_slam_component.cpp:267-319) behind `lsr_optimize_pose_graph` — g2o's VertexSE3 / EdgeSE3 graph with identity information,
-vertex 0 fixed, ten Levenberg-Marquardt iterations, solved on the device; no g2o.
+(graph_based_slam_component.cpp:267-319) behind `lsr_optimize_pose_graph_long` — g2o's VertexSE3 / EdgeSE3 graph with identity information,
+vertex 0 fixed, ten Levenberg-Marquardt iterations, solved on the device; no g2o.  Up to 1024 edges outside the band (every loop edge a
+node has accepted over a few laps); within the 64 of `lsr_optimize_pose_graph` the result is that entry's, bit for bit.
 
 An edge is `(from, to, Z)` with Z the 4x4 fp64 measurement from^-1 * to — what `LoopEdge.relative_pose` holds.  `adjacent_edges` makes
 the odometry edges the reference adds (:289-303), `optimize` runs the optimiser; `MapArray.pose_adjustment` chains both behind the
@@ -57,8 +58,12 @@ def adjacent_edges(poses, k: int = NUM_ADJACENT_POSE_CONSTRAINTS) -> List[Tuple[
 
 
 def optimize(registration, poses, edges: Sequence[Tuple[int, int, np.ndarray]], max_iterations: int = 10,
-             band: int = NUM_ADJACENT_POSE_CONSTRAINTS):
-    """optimizer.optimize(max_iterations) (:317-318) on the device of `registration`.  -> ((n, 4, 4) fp64 poses, PoseGraphResult)."""
+             band: int = NUM_ADJACENT_POSE_CONSTRAINTS, entry: str = "lsr_optimize_pose_graph_long"):
+    """optimizer.optimize(max_iterations) (:317-318) on the device of `registration`, through lsr_optimize_pose_graph_long: up to
+    _capi.POSE_GRAPH_LONG_MAX_OFFBAND_EDGES edges with |from - to| > band.  `entry`: the C entry point; "lsr_optimize_pose_graph" keeps
+    its limit of _capi.POSE_GRAPH_MAX_OFFBAND_EDGES (the same bits within it).  -> ((n, 4, 4) fp64 poses, PoseGraphResult)."""
+    if entry not in ("lsr_optimize_pose_graph_long", "lsr_optimize_pose_graph"):
+        raise ValueError("entry: lsr_optimize_pose_graph_long or lsr_optimize_pose_graph")
     lib = _capi.load()
     P = _col16(poses)
     n, m = len(P), len(edges)
@@ -70,7 +75,7 @@ def optimize(registration, poses, edges: Sequence[Tuple[int, int, np.ndarray]], 
     out = np.zeros((n, 16), np.float64)
     res = _capi.PoseGraphResult()
     trace = (_capi.PoseGraphTrace * max(int(max_iterations), 1))()
-    _capi.check(lib.lsr_optimize_pose_graph(registration._h, _dp(P), n, arr, m, C.byref(params), _dp(out), C.byref(res), trace),
+    _capi.check(getattr(lib, entry)(registration._h, _dp(P), n, arr, m, C.byref(params), _dp(out), C.byref(res), trace),
                 "optimizePoseGraph")
     tr = [dict(trials=t.trials, chi2=t.chi2, lam=t.lam, rho=t.rho) for t in trace[:res.iterations]]
     return (out.reshape(n, 4, 4).transpose(0, 2, 1).copy(),

@@ -429,10 +429,11 @@ class Registration:
         return flat[: n_out.value * out_step].reshape(n_out.value, out_step), np.array(first[:], np.int64)
 
     def optimizePoseGraph(self, poses, edges, max_iterations: int = 10, band: int = 5):
-        """The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319) through lsr_optimize_pose_graph: g2o's
+        """The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319) through lsr_optimize_pose_graph_long: g2o's
         VertexSE3 / EdgeSE3 graph (identity information, vertex 0 fixed) under its Levenberg-Marquardt controller, on this object's
         device.  `poses`: (n, 4, 4) fp64; `edges`: (from, to, 4x4 measurement from^-1 * to) — pose_graph.adjacent_edges(poses) followed by
-        the loop edges.  Returns ((n, 4, 4) fp64 poses — what assembleMap takes as `poses` —, pose_graph.PoseGraphResult)."""
+        the loop edges, up to 1024 of them outside the band.  Returns ((n, 4, 4) fp64 poses — what assembleMap takes as `poses` —,
+        pose_graph.PoseGraphResult)."""
         from . import pose_graph
 
         return pose_graph.optimize(self, poses, edges, max_iterations, band)
