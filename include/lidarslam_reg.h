@@ -41,7 +41,8 @@ typedef enum lsr_status {
   LSR_ERR_NO_SOURCE = -5,       /* align/getFitnessScore before setInputSource */
   LSR_ERR_NOT_IMPLEMENTED = -6, /* (no entry returns it at present; until round 6 the NDT neighbourhood KDTREE did) */
   LSR_ERR_INDEX_OVERFLOW = -7,  /* voxel index space exceeds int32 (PCL: "Leaf size is too small") */
-  LSR_ERR_TOO_FEW_POINTS = -8   /* GICP: cloud smaller than k_correspondences */
+  LSR_ERR_TOO_FEW_POINTS = -8,  /* GICP: cloud smaller than k_correspondences */
+  LSR_ERR_IO = -9               /* a file could not be opened or written (lsr_save_pcd_ascii); errno's text in lsr_last_error() */
 } lsr_status;
 
 /* registration_method: scanmatcher_component.cpp:103-124, graph_based_slam_component.cpp:63-86 */
@@ -73,6 +74,9 @@ typedef enum lsr_key {
                                          [ms]: the right-hand sides and the 1 + 6L band solves; */
   LSR_POSE_GRAPH_DENSE_MS = 10,       /* the dense part (C = I + U B^-1 U^T formed, factored and solved); */
   LSR_POSE_GRAPH_COMBINE_MS = 11,     /* the row combine x = B^-1 b - B^-1 U^T z.  Else 0 */
+  LSR_PCD_FORMAT_MS = 12,             /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the formatting launches
+                                         (length pass, scan, write pass; copies outside the brackets) of the last lsr_format_pcd_ascii /
+                                         lsr_save_pcd_ascii / lsr_save_map_pcd_ascii on this object, summed over its pieces; else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -114,9 +118,12 @@ typedef enum lsr_key {
                                          the current target (GICP: neighbour grid and k-NN covariances computed with this object's
                                          k_correspondences / gicp_epsilon; NDT: voxel grid at this object's resolution), 0 = the next
                                          align builds something first, or there is no target */
-  LSR_MAP_ASSEMBLY_FORM = 49          /* read-only (lsr_get_i32): which form the last lsr_assemble_map on this object took: 0 = none yet,
+  LSR_MAP_ASSEMBLY_FORM = 49,         /* read-only (lsr_get_i32): which form the last lsr_assemble_map on this object took: 0 = none yet,
                                          1 = wide (both layouts {32; 0,4,8,16}, every base pointer 16-byte aligned: two 16-byte loads
                                          and two 16-byte stores per record), 2 = general (any layout).  The bytes are the same */
+  LSR_PCD_PIECE_RECORDS = 50          /* records per piece of lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (64 .. 1 << 22, default 1 << 20): a
+                                         piece is formatted and copied while the calling thread writes the one before it.  The file's
+                                         bytes do not depend on it */
 } lsr_key;
 /* Environment presets read when an object is created: LSR_NDT_WORKGROUP, LSR_NDT_TABLE_MODE, LSR_NDT_QUAD, LSR_GRID_BUILDER,
  * LSR_WAIT_MODE (the keys above); LSR_NDT_CHAINS=1|2|3 fixes the number of independent launch chains a candidate set runs as (default: two
@@ -446,7 +453,7 @@ typedef struct lsr_loop_edge {
  * pose it reports.
  * The pose-graph optimisation that follows (doPoseAdjustment, :267-319) is lsr_optimize_pose_graph below — no g2o needed —, and what the
  * caller does with the optimiser's poses right afterwards — every submap moved by its new pose, the whole map put together — is
- * lsr_assemble_map. */
+ * lsr_assemble_map; the map.pcd the function ends with (:369) is lsr_save_map_pcd_ascii. */
 int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, size_t stride_bytes, int on_device,
                     const lsr_loop_params* params, lsr_loop_edge* edges, int edge_capacity, int* n_evaluated);
 
@@ -478,6 +485,39 @@ int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, si
 int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
                      const double* poses16 /* nullable */, void* out_data, size_t capacity_points,
                      const lsr_pc2_layout* out_layout, int out_on_device, size_t* first_record /* nullable */, size_t* n_out);
+
+/* ---- map.pcd -------------------------------------------------------- */
+/* pcl::io::savePCDFileASCII("map.pcd", *map_ptr) at the end of doPoseAdjustment (graph_based_slam_component.cpp:369, "too heavy"; reached
+ * by the map_save service, :96-103, and by every accepted loop closure under use_save_map_in_loop): the file's bytes are formatted on the
+ * device.  The format (restated, unpinned): the v0.7 header of a cloud of width n and height 1 with default viewpoint —
+ * FIELDS x y z intensity, or x y z for a layout with offset_intensity < 0 —, then one line per record in record order, the fields
+ * separated by one blank, each the C library's "%.8g" of the float promoted to double (exact binary value, correctly rounded to 8
+ * significant digits, ties to even; trailing zeros dropped; exponent form below 1e-4 and from 1e8; "-0"; "inf" / "-inf"), any NaN "nan". */
+#define LSR_PCD_ASCII_MAX_LINE_BYTES 60    /* four fields of 14 bytes ("-1.1754944e-38"), three blanks, the newline */
+#define LSR_PCD_ASCII_MAX_HEADER_BYTES 256 /* the header is shorter than this */
+/* The whole file image, header and body, of n_points records of `layout` (host pointer, or HIP device pointer with on_device != 0) into
+ * out_text (host, or HIP device buffer with out_on_device != 0; any alignment) of capacity_bytes; *n_bytes = the image's size.
+ * out_text == NULL: only *n_bytes is set (the length pass runs; capacity_bytes is ignored).  Layout rules and the ordering rules of device
+ * inputs: as for lsr_assemble_map.  Returns when the text is complete, for a reader on any stream.
+ * LSR_ERR_INVALID_ARGUMENT: null handle, data, layout or n_bytes; a layout lsr_assemble_map refuses; data or a field not 4-byte aligned;
+ * n_points == 0 (PCL refuses an empty cloud too); capacity_bytes below the size.  LSR_ERR_INDEX_OVERFLOW: more than INT32_MAX records.
+ * No error touches out_text or *n_bytes.  What the object answers afterwards (target, source, final transformation, fitness) is unchanged,
+ * as for the two entries below. */
+int lsr_format_pcd_ascii(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, int on_device, void* out_text,
+                         size_t capacity_bytes, int out_on_device, size_t* n_bytes);
+/* The same image written to the file `path` (created or truncated), in pieces of LSR_PCD_PIECE_RECORDS records through two pinned buffers
+ * kept on the object: piece k + 1 is formatted and copied on the object's stream while the calling thread fwrites piece k.  A host input
+ * is staged piece by piece.  The file's bytes do not depend on the piece size or on where the input lives.  *n_bytes = the file's size.
+ * Errors as above, and LSR_ERR_INVALID_ARGUMENT for a null path; LSR_ERR_IO, with errno's text in lsr_last_error(), when the file cannot
+ * be opened or a write comes up short.  On any error after the file was opened it is closed and removed. */
+int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t n_points, const lsr_pc2_layout* layout, int on_device,
+                       size_t* n_bytes);
+/* `if (do_save_map) pcl::io::savePCDFileASCII("map.pcd", *map_ptr)` (:369) in one call: lsr_assemble_map of the submaps (same arguments,
+ * same launch, hence the same coordinate bits) into a device buffer of pcl::PointXYZI records {32; 0, 4, 8, 16} kept on the object, then
+ * lsr_save_pcd_ascii from that buffer.  The file is byte-equal to those two calls made one after the other.  Errors: those of the two;
+ * a map without any record is LSR_ERR_INVALID_ARGUMENT. */
+int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
+                           int on_device, const double* poses16 /* nullable */, size_t* n_bytes);
 
 /* ---- pose-graph optimisation --------------------------------------------- */
 /* The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319): g2o's VertexSE3 / EdgeSE3 graph with identity

@@ -1,0 +1,69 @@
+// lidarslam_reg/pcd_io.hpp — header-only helpers over lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (lidarslam_reg.h): map.pcd written
+// from the device, the bytes pcl::io::savePCDFileASCII writes.
+//
+//   graph_based_slam/src/graph_based_slam_component.cpp:369   if (do_save_map) {pcl::io::savePCDFileASCII("map.pcd", *map_ptr);} // too heavy
+//
+// Needs neither PCL nor Eigen nor HIP: a pose is anything whose .matrix().data() yields 16 column-major doubles (Eigen::Isometry3d,
+// Eigen::Affine3d — g2o's vertex->estimate()).  INTEGRATION.md §3g shows the call site replaced.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../lidarslam_reg.h"
+
+namespace lidarslam_reg {
+
+// pcl::PointXYZI as pcl::toROSMsg lays it out: what SubMap.cloud holds
+inline lsr_pc2_layout pcdPointXYZILayout() { return lsr_pc2_layout{32u, 0u, 4u, 8u, 16}; }
+
+// pcl::io::savePCDFileASCII(path, cloud) for n records of `layout` in `payload` (a PointCloud2's data; host memory, or a HIP device
+// pointer with payload_on_device).  Reports like the registration adapter does (stderr, false); a file that could not be completed is
+// removed.  n_bytes (nullable) receives the file's size.
+inline bool savePCDFileASCII(lsr_handle h, const std::string& path, const void* payload, size_t n,
+                             const lsr_pc2_layout& layout = pcdPointXYZILayout(), bool payload_on_device = false, size_t* n_bytes = nullptr) {
+  size_t bytes = 0;
+  const int st = lsr_save_pcd_ascii(h, path.c_str(), payload, n, &layout, payload_on_device ? 1 : 0, &bytes);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::savePCDFileASCII] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_bytes) *n_bytes = bytes;
+  return true;
+}
+
+// The whole map of a MapArray as map.pcd in one call: every submap moved by its pose on the device — poses16_or_null: submaps.size()
+// column-major fp64 4x4 matrices, or nullptr = every submap's own position / orientation —, the map kept in HBM, its text formatted
+// there and written piece by piece.  The records are those lsr_assemble_map gives the same arguments.
+inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<lsr_submap>& submaps, const double* poses16_or_null,
+                       bool submaps_on_device = false, const lsr_pc2_layout& in_layout = pcdPointXYZILayout(), size_t* n_bytes = nullptr) {
+  size_t bytes = 0;
+  const int st = lsr_save_map_pcd_ascii(h, path.c_str(), submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0,
+                                        poses16_or_null, &bytes);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::saveMapPCD] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_bytes) *n_bytes = bytes;
+  return true;
+}
+
+// The same with the optimiser's poses as objects: Pose::matrix().data() = 16 column-major doubles.  poses_or_null: submaps.size()
+// entries, or nullptr = the submaps' own poses.
+template <typename Pose>
+inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<lsr_submap>& submaps, const Pose* poses_or_null,
+                       bool submaps_on_device = false) {
+  if (!poses_or_null) return saveMapPCD(h, path, submaps, static_cast<const double*>(nullptr), submaps_on_device);
+  std::vector<double> poses16(16 * submaps.size());
+  for (size_t i = 0; i < submaps.size(); i++) {
+    const auto M = poses_or_null[i].matrix();
+    std::memcpy(poses16.data() + 16 * i, M.data(), 16 * sizeof(double));
+  }
+  return saveMapPCD(h, path, submaps, poses16.data(), submaps_on_device);
+}
+
+}  // namespace lidarslam_reg

@@ -21,6 +21,9 @@ KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
 (RESOLUTION, TRANSFORMATION_EPSILON, STEP_SIZE, OUTLIER_RATIO, MAX_CORRESPONDENCE_DISTANCE, ROTATION_EPSILON,
  EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON, MAP_ASSEMBLY_MS, POSE_GRAPH_BAND_SOLVE_MS, POSE_GRAPH_DENSE_MS,
  POSE_GRAPH_COMBINE_MS) = range(12)
+PCD_FORMAT_MS, PCD_PIECE_RECORDS = 12, 50
+ERR_IO = -9
+PCD_ASCII_MAX_LINE_BYTES, PCD_ASCII_MAX_HEADER_BYTES = 60, 256
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
  HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED,
  MAP_ASSEMBLY_FORM) = range(32, 50)
@@ -38,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
     "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
     "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long",
+    "lsr_format_pcd_ascii", "lsr_save_pcd_ascii", "lsr_save_map_pcd_ascii",
 ]
 
 
@@ -159,6 +163,9 @@ def load() -> C.CDLL:
                                   C.POINTER(LoopEdge), C.c_int, ip]
     L.lsr_assemble_map.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, vp, C.c_size_t, C.POINTER(Pc2Layout),
                                    C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.lsr_format_pcd_ascii.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_save_pcd_ascii.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_save_map_pcd_ascii.argtypes = [vp, C.c_char_p, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, C.POINTER(C.c_size_t)]
     L.lsr_pose_graph_edges.argtypes = [dp, C.c_int, C.c_int, C.POINTER(PoseEdge), C.c_size_t, C.POINTER(C.c_size_t)]
     for name in ("lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long"):
         getattr(L, name).argtypes = [vp, dp, C.c_int, C.POINTER(PoseEdge), C.c_int, C.POINTER(PoseGraphParams), dp,

@@ -1,7 +1,10 @@
 // C ABI of the registration core (include/lidarslam_reg.h).  Host-side orchestration only:
 // device buffers, launch chains, result read-back.  No CPU fallback exists — every compute
 // entry point runs HIP kernels on a gfx950 device or returns an error status.
+#include <sys/stat.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <functional>
 #include <limits>
@@ -790,6 +793,7 @@ const char* lsr_status_string(int status) {
     case LSR_ERR_NOT_IMPLEMENTED: return "not implemented";
     case LSR_ERR_INDEX_OVERFLOW: return "voxel index overflow";
     case LSR_ERR_TOO_FEW_POINTS: return "too few points";
+    case LSR_ERR_IO: return "file input/output error";
     default: return "unknown status";
   }
 }
@@ -923,6 +927,7 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_POSE_GRAPH_BAND_SOLVE_MS: *v = h->pose_graph.stage_ms[0]; return LSR_OK;
     case LSR_POSE_GRAPH_DENSE_MS: *v = h->pose_graph.stage_ms[1]; return LSR_OK;
     case LSR_POSE_GRAPH_COMBINE_MS: *v = h->pose_graph.stage_ms[2]; return LSR_OK;
+    case LSR_PCD_FORMAT_MS: *v = h->pcd.format_ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -969,6 +974,9 @@ int lsr_set_i32(lsr_handle h, int key, int v) {
     case LSR_WAIT_MODE:
       if (v < 0 || v > 2) { set_last_error("wait mode must be 0 (spin), 1 (yield) or 2 (sleep)"); return LSR_ERR_INVALID_ARGUMENT; }
       h->scratch.wait_mode = v; return LSR_OK;
+    case LSR_PCD_PIECE_RECORDS:
+      if (v < PCD_PIECE_MIN || v > PCD_PIECE_MAX) { set_last_error("PCD piece size must be in 64 .. 1 << 22 records"); return LSR_ERR_INVALID_ARGUMENT; }
+      h->pcd.piece_records = v; return LSR_OK;
     default: set_last_error("unknown i32 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -993,6 +1001,7 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_WAIT_MODE: *v = h->scratch.wait_mode; return LSR_OK;
     case LSR_VOXEL_FILTER_FORM: *v = h->scratch.vg_form; return LSR_OK;
     case LSR_MAP_ASSEMBLY_FORM: *v = h->map_form; return LSR_OK;
+    case LSR_PCD_PIECE_RECORDS: *v = h->pcd.piece_records; return LSR_OK;
     case LSR_TARGET_PREPARED:
       if (h->method == LSR_METHOD_GICP) *v = gicp_target_prepared(h) ? 1 : 0;
       else *v = (h->target && h->target->n > 0 && h->target->has_grid && h->target->grid_leaf == (float)h->ndt.resolution &&
@@ -2008,6 +2017,223 @@ int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, c
   h->map_form = wide ? 1 : 2;
   h->map_ms = map_ms;
   return finish();
+}
+
+// ---- N7: map.pcd -------------------------------------------------------------------------------
+// pcl::io::savePCDFileASCII("map.pcd", *map_ptr) (graph_based_slam_component.cpp:369): the text is formatted on the device (pcd_text.hip).
+namespace {
+int pcd_check_args(const void* data, size_t n, const lsr_pc2_layout* layout, PcdFields* F) {
+  if (!data) { set_last_error("null record pointer"); return LSR_ERR_INVALID_ARGUMENT; }
+  int st = check_layout(layout);
+  if (st) return st;
+  if ((uintptr_t)data & 3) { set_last_error("records are not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (n == 0) { set_last_error("an empty cloud has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (n > (size_t)INT32_MAX) { set_last_error("more than INT32_MAX records"); return LSR_ERR_INDEX_OVERFLOW; }
+  F->step = (int)layout->point_step;
+  F->n_fields = layout->offset_intensity >= 0 ? 4 : 3;
+  F->off[0] = (int)layout->offset_x; F->off[1] = (int)layout->offset_y; F->off[2] = (int)layout->offset_z;
+  F->off[3] = layout->offset_intensity >= 0 ? layout->offset_intensity : 0;
+  return LSR_OK;
+}
+// a bracket whose second event has completed
+int pcd_add_ms(hipEvent_t a, hipEvent_t b, double* ms) {
+  float t = 0.f;
+  LSR_HIP(hipEventElapsedTime(&t, a, b));
+  *ms += t;
+  return LSR_OK;
+}
+int pcd_io_error(const char* what, const char* path) {
+  set_last_error(std::string(what) + " " + path + ": " + std::strerror(errno));
+  return LSR_ERR_IO;
+}
+// the file being written: closed and removed unless the call gets as far as commit() (a device node such as /dev/null is only closed)
+struct PcdFile {
+  FILE* f = nullptr;
+  const char* path = nullptr;
+  bool regular = false;
+  ~PcdFile() {
+    if (!f) return;
+    (void)std::fclose(f);
+    if (regular) (void)std::remove(path);
+  }
+  int commit() {
+    FILE* g = f;
+    f = nullptr;
+    if (std::fclose(g) == 0) return 0;
+    const int e = errno;
+    if (regular) (void)std::remove(path);
+    errno = e;
+    return -1;
+  }
+};
+struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
+}  // namespace
+
+int lsr_format_pcd_ascii(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, int on_device, void* out_text,
+                         size_t capacity_bytes, int out_on_device, size_t* n_bytes) {
+  LSR_CHECK_HANDLE(h);
+  if (!n_bytes) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
+  PcdFields F;
+  int st = pcd_check_args(data, n_points, layout, &F);
+  if (st) return st;
+  PcdState& S = h->pcd;
+  const size_t nb = pcd_blocks(n_points);
+  if ((st = S.ensure_events()) || (st = S.block_sums[0].reserve(nb)) || (st = S.offsets[0].reserve(nb + 1)) || (st = S.totals.reserve(2)) ||
+      (st = S.header.reserve(PCD_MAX_HEADER_BYTES)))
+    return st;
+  // whatever was enqueued has finished before the call returns: the staging buffer and the caller's buffers are free again
+  StreamDrain drain{h->stream};
+  const void* d = data;
+  if (!on_device) {
+    if ((st = h->staging.reserve(n_points * F.step))) return st;
+    LSR_HIP(hipMemcpyAsync(h->staging.p, data, n_points * F.step, hipMemcpyHostToDevice, h->stream));
+    d = h->staging.p;
+  }
+  hipEvent_t* ev = S.ev[0];
+  if (h->profile) LSR_HIP(hipEventRecord(ev[PcdState::EV_L0], h->stream));
+  if ((st = pcd_text_lengths(d, n_points, F, S.block_sums[0].p, S.offsets[0].p, h->stream))) return st;
+  if (h->profile) LSR_HIP(hipEventRecord(ev[PcdState::EV_L1], h->stream));
+  LSR_HIP(hipMemcpyAsync(S.totals.p, S.offsets[0].p + nb, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  const size_t body = (size_t)S.totals.p[0];
+  char header[PCD_MAX_HEADER_BYTES];
+  const size_t header_bytes = (size_t)pcd_header_text(n_points, F.n_fields == 4, header);
+  const size_t size = header_bytes + body;
+  double ms = 0.0;
+  if (h->profile && (st = pcd_add_ms(ev[PcdState::EV_L0], ev[PcdState::EV_L1], &ms))) return st;
+  if (!out_text) {
+    S.format_ms = ms;
+    *n_bytes = size;
+    return LSR_OK;
+  }
+  if (capacity_bytes < size) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
+  unsigned char* d_text = nullptr;
+  if (out_on_device) {
+    std::memcpy(S.header.p, header, header_bytes);
+    LSR_HIP(hipMemcpyAsync(out_text, S.header.p, header_bytes, hipMemcpyHostToDevice, h->stream));
+    d_text = static_cast<unsigned char*>(out_text) + header_bytes;
+  } else {
+    if ((st = S.text.reserve(body))) return st;
+    d_text = S.text.p;
+  }
+  if (h->profile) LSR_HIP(hipEventRecord(ev[PcdState::EV_W0], h->stream));
+  if ((st = pcd_text_write(d, n_points, F, S.offsets[0].p, d_text, h->stream))) return st;
+  if (h->profile) LSR_HIP(hipEventRecord(ev[PcdState::EV_W1], h->stream));
+  if (!out_on_device)
+    LSR_HIP(hipMemcpyAsync(static_cast<unsigned char*>(out_text) + header_bytes, S.text.p, body, hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  if (!out_on_device) std::memcpy(out_text, header, header_bytes);
+  if (h->profile && (st = pcd_add_ms(ev[PcdState::EV_W0], ev[PcdState::EV_W1], &ms))) return st;
+  S.format_ms = ms;
+  *n_bytes = size;
+  return LSR_OK;
+}
+
+int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t n_points, const lsr_pc2_layout* layout, int on_device,
+                       size_t* n_bytes) {
+  LSR_CHECK_HANDLE(h);
+  if (!path || !n_bytes) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
+  PcdFields F;
+  int st = pcd_check_args(data, n_points, layout, &F);
+  if (st) return st;
+  PcdState& S = h->pcd;
+  const size_t P = (size_t)S.piece_records, n_pieces = (n_points + P - 1) / P, p_max = std::min(P, n_points);
+  const size_t nb_max = pcd_blocks(p_max), text_max = p_max * PCD_MAX_LINE_BYTES;
+  if ((st = S.ensure_events()) || (st = S.totals.reserve(2)) || (st = S.text.reserve(text_max))) return st;
+  for (int par = 0; par < 2; par++)
+    if ((st = S.block_sums[par].reserve(nb_max)) || (st = S.offsets[par].reserve(nb_max + 1)) || (st = S.pin[par].reserve(text_max))) return st;
+  const bool in_host = on_device == 0;
+  if (in_host && (st = h->staging.reserve(2 * p_max * F.step))) return st;
+
+  PcdFile file;
+  file.path = path;
+  file.f = std::fopen(path, "wb");
+  if (!file.f) return pcd_io_error("cannot open", path);
+  {
+    struct stat sb;
+    file.regular = fstat(fileno(file.f), &sb) == 0 && S_ISREG(sb.st_mode);
+  }
+  StreamDrain drain{h->stream};   // (destroyed before `file`: nothing is in flight when the file is closed)
+  char header[PCD_MAX_HEADER_BYTES];
+  const size_t header_bytes = (size_t)pcd_header_text(n_points, F.n_fields == 4, header);
+  if (std::fwrite(header, 1, header_bytes, file.f) != header_bytes) return pcd_io_error("short write to", path);
+  size_t written = header_bytes;
+  double ms = 0.0;
+
+  const void* d_piece[2] = {nullptr, nullptr};
+  size_t count[2] = {0, 0}, bytes[2] = {0, 0};
+  // stream order: len(k + 1) | write(k) copy(k) | len(k + 2) | write(k + 1) ... — the host learns a piece's size one piece ahead of
+  // laying it out, and writes piece k - 1 to the file while the device works on the three steps in front of it
+  auto enqueue_lengths = [&](size_t k) -> int {
+    const int par = (int)(k & 1);
+    const size_t first = k * P, cnt = std::min(P, n_points - first);
+    const unsigned char* src = static_cast<const unsigned char*>(data) + first * F.step;
+    if (in_host) {
+      unsigned char* stage = h->staging.p + (size_t)par * p_max * F.step;
+      LSR_HIP(hipMemcpyAsync(stage, src, cnt * F.step, hipMemcpyHostToDevice, h->stream));
+      src = stage;
+    }
+    d_piece[par] = src;
+    count[par] = cnt;
+    if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_L0], h->stream));
+    int e = pcd_text_lengths(src, cnt, F, S.block_sums[par].p, S.offsets[par].p, h->stream);
+    if (e) return e;
+    if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_L1], h->stream));
+    LSR_HIP(hipMemcpyAsync(S.totals.p + par, S.offsets[par].p + pcd_blocks(cnt), sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_LEN], h->stream));
+    return LSR_OK;
+  };
+  auto flush = [&](size_t k) -> int {
+    const int par = (int)(k & 1);
+    LSR_HIP(hipEventSynchronize(S.ev[par][PcdState::EV_DONE]));
+    if (h->profile) {
+      int e = pcd_add_ms(S.ev[par][PcdState::EV_W0], S.ev[par][PcdState::EV_W1], &ms);
+      if (e) return e;
+    }
+    if (std::fwrite(S.pin[par].p, 1, bytes[par], file.f) != bytes[par]) return pcd_io_error("short write to", path);
+    written += bytes[par];
+    return LSR_OK;
+  };
+
+  if ((st = enqueue_lengths(0))) return st;
+  for (size_t k = 0; k < n_pieces; k++) {
+    const int par = (int)(k & 1);
+    LSR_HIP(hipEventSynchronize(S.ev[par][PcdState::EV_LEN]));
+    bytes[par] = (size_t)S.totals.p[par];
+    if (bytes[par] > count[par] * PCD_MAX_LINE_BYTES) { set_last_error("a piece's text is longer than its bound"); return LSR_ERR_HIP; }
+    if (h->profile && (st = pcd_add_ms(S.ev[par][PcdState::EV_L0], S.ev[par][PcdState::EV_L1], &ms))) return st;
+    if (k + 1 < n_pieces && (st = enqueue_lengths(k + 1))) return st;
+    if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_W0], h->stream));
+    if ((st = pcd_text_write(d_piece[par], count[par], F, S.offsets[par].p, S.text.p, h->stream))) return st;
+    if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_W1], h->stream));
+    LSR_HIP(hipMemcpyAsync(S.pin[par].p, S.text.p, bytes[par], hipMemcpyDeviceToHost, h->stream));
+    LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_DONE], h->stream));
+    if (k >= 1 && (st = flush(k - 1))) return st;
+  }
+  if ((st = flush(n_pieces - 1))) return st;
+  if (file.commit() != 0) return pcd_io_error("cannot close", path);
+  S.format_ms = ms;
+  *n_bytes = written;
+  return LSR_OK;
+}
+
+int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
+                           int on_device, const double* poses16, size_t* n_bytes) {
+  LSR_CHECK_HANDLE(h);
+  if (!path || !n_bytes || !submaps || num_submaps <= 0) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
+  size_t total = 0;
+  for (int i = 0; i < num_submaps; i++)
+    if (submaps[i].n_points > (size_t)INT32_MAX || (total += submaps[i].n_points) > (size_t)INT32_MAX) {
+      set_last_error("the map holds more than INT32_MAX records");
+      return LSR_ERR_INDEX_OVERFLOW;
+    }
+  if (total == 0) { set_last_error("an empty map has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }
+  static const lsr_pc2_layout xyzi = {32, 0, 4, 8, 16};   // pcl::PointXYZI, what map_ptr holds
+  int st = h->pcd.map.reserve(total * xyzi.point_step);
+  if (st) return st;
+  size_t n = 0;
+  if ((st = lsr_assemble_map(h, submaps, num_submaps, in_layout, on_device, poses16, h->pcd.map.p, total, &xyzi, 1, nullptr, &n))) return st;
+  return lsr_save_pcd_ascii(h, path, h->pcd.map.p, n, &xyzi, 1, n_bytes);
 }
 
 int lsr_pose_graph_edges(const double* poses16, int n, int num_adjacent, lsr_pose_edge* out, size_t capacity, size_t* n_out) {

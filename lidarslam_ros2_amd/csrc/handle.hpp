@@ -5,6 +5,7 @@
 #include "gicp.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
+#include "pcd_text.hpp"
 #include "pose_graph.hpp"
 
 namespace lsr {
@@ -92,6 +93,8 @@ struct lsr_handle_s {
   lsr::DeskewState deskew;   // IMU queue and de-skew scratch (use_imu frontend path, csrc/deskew.hip)
 
   lsr::PgWorkspace pose_graph;   // lsr_optimize_pose_graph (csrc/pose_graph.hip): device buffers, kept between calls
+
+  lsr::PcdState pcd;   // lsr_format_pcd_ascii / lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (csrc/pcd_text.hip): buffers, kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1): one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

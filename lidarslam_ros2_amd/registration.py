@@ -13,6 +13,7 @@ column-major order at the boundary).
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -375,30 +376,8 @@ class Registration:
         if n == 0:
             raise ValueError("assembleMap needs at least one submap")
         li, lo = self._layout(*in_layout), self._layout(*out_layout)
-        in_step, out_step = int(in_layout[0]), int(out_layout[0])
-        arr = (capi.SubMap * n)()
-        keep, residency = [], None
-        for i, sm in enumerate(submaps):
-            ptr, cnt, dev, holder = _record_args(sm.cloud, in_step)
-            keep.append(holder)
-            if cnt:
-                if residency is None:
-                    residency = dev
-                elif dev != residency:
-                    raise ValueError("all submap clouds must share residency (host/device)")
-            arr[i].position[:] = [float(v) for v in sm.position]
-            arr[i].orientation[:] = [float(v) for v in sm.orientation]
-            arr[i].distance = float(getattr(sm, "distance", 0.0))
-            arr[i].cloud = ptr if cnt else None
-            arr[i].n_points = cnt
-        if residency is None:
-            residency = any(_is_torch_cuda(h) for h in keep)
-        total = int(sum(a.n_points for a in arr))
-        P = None
-        if poses is not None:
-            if len(poses) != n:
-                raise ValueError("one pose per submap")
-            P = np.ascontiguousarray(np.stack([np.asarray(p, np.float64).reshape(4, 4).T.reshape(16) for p in poses]), np.float64)
+        out_step = int(out_layout[0])
+        arr, keep, residency, total, P = self._submap_table(submaps, poses, int(in_layout[0]))
         if out is None:
             if residency:
                 import torch
@@ -427,6 +406,106 @@ class Registration:
                                               P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.c_void_p(optr), cap,
                                               C.byref(lo), 1 if out_dev else 0, first, C.byref(n_out)), "assembleMap")
         return flat[: n_out.value * out_step].reshape(n_out.value, out_step), np.array(first[:], np.int64)
+
+    def _submap_table(self, submaps, poses, in_step: int):
+        """The lsr_submap array of assembleMap / saveMapPCDFileASCII -> (array, keepalives, on_device, total records, column-major
+        poses or None)."""
+        n = len(submaps)
+        arr = (capi.SubMap * n)()
+        keep, residency = [], None
+        for i, sm in enumerate(submaps):
+            ptr, cnt, dev, holder = _record_args(sm.cloud, in_step)
+            keep.append(holder)
+            if cnt:
+                if residency is None:
+                    residency = dev
+                elif dev != residency:
+                    raise ValueError("all submap clouds must share residency (host/device)")
+            arr[i].position[:] = [float(v) for v in sm.position]
+            arr[i].orientation[:] = [float(v) for v in sm.orientation]
+            arr[i].distance = float(getattr(sm, "distance", 0.0))
+            arr[i].cloud = ptr if cnt else None
+            arr[i].n_points = cnt
+        if residency is None:
+            residency = any(_is_torch_cuda(h) for h in keep)
+        total = int(sum(a.n_points for a in arr))
+        P = None
+        if poses is not None:
+            if len(poses) != n:
+                raise ValueError("one pose per submap")
+            P = np.ascontiguousarray(np.stack([np.asarray(p, np.float64).reshape(4, 4).T.reshape(16) for p in poses]), np.float64)
+        return arr, keep, residency, total, P
+
+    # -- map.pcd (SURVEY.md 8f N7) ---------------------------------------------------------------------
+    def formatPCDASCII(self, records, layout=PC2_XYZI, out=None):
+        """The bytes pcl::io::savePCDFileASCII writes for a cloud of these records (header and body, SURVEY.md 9.10), formatted on the
+        device through lsr_format_pcd_ascii.  `records`: a record buffer of `layout` — numpy array (-> uint8 numpy array) or CUDA
+        tensor (-> uint8 CUDA tensor, nothing leaves HBM).  `out`: None = a new buffer, or a contiguous uint8 buffer to write; the
+        result is the view of it that holds the text."""
+        lay = self._layout(*layout)
+        ptr, n, dev, keep = _record_args(records, int(layout[0]))
+        if dev:
+            _order_after_torch(self, keep)
+        size = C.c_size_t()
+        if out is None:
+            capi.check(self._lib.lsr_format_pcd_ascii(self._h, C.c_void_p(ptr), n, C.byref(lay), 1 if dev else 0, None, 0, 0, C.byref(size)),
+                       "formatPCDASCII")
+            if dev:
+                import torch
+
+                out = torch.empty(size.value, dtype=torch.uint8, device=torch.device("cuda", self._device))
+            else:
+                out = np.zeros(size.value, np.uint8)
+        out_dev = _is_torch_cuda(out)
+        if out_dev:
+            if not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out must be a contiguous uint8 buffer")
+            flat, optr, cap = out.view(-1), out.data_ptr(), out.numel()
+            _order_after_torch(self, out)
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError("out must be a writeable contiguous uint8 buffer")
+            flat, optr, cap = out.reshape(-1), out.ctypes.data, out.nbytes
+        capi.check(self._lib.lsr_format_pcd_ascii(self._h, C.c_void_p(ptr), n, C.byref(lay), 1 if dev else 0, C.c_void_p(optr), cap,
+                                                  1 if out_dev else 0, C.byref(size)), "formatPCDASCII")
+        return flat[: size.value]
+
+    def savePCDFileASCII(self, path, records, layout=PC2_XYZI) -> int:
+        """pcl::io::savePCDFileASCII(path, cloud) through lsr_save_pcd_ascii: the same bytes, formatted on the device piece by piece
+        while this thread writes the file.  `records` as for formatPCDASCII.  Returns the file's size in bytes."""
+        lay = self._layout(*layout)
+        ptr, n, dev, keep = _record_args(records, int(layout[0]))
+        if dev:
+            _order_after_torch(self, keep)
+        size = C.c_size_t()
+        capi.check(self._lib.lsr_save_pcd_ascii(self._h, os.fsencode(path), C.c_void_p(ptr), n, C.byref(lay), 1 if dev else 0, C.byref(size)),
+                   "savePCDFileASCII")
+        return int(size.value)
+
+    def saveMapPCDFileASCII(self, path, submaps, poses=None, in_layout=PC2_XYZI) -> int:
+        """`if (do_save_map) pcl::io::savePCDFileASCII("map.pcd", *map_ptr)` (graph_based_slam_component.cpp:369) in one call
+        (lsr_save_map_pcd_ascii): the submaps moved by their poses (`poses`: None = their own, or the optimiser's, as for assembleMap)
+        into a map that stays on the device, and that map written as text.  Returns the file's size in bytes."""
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("saveMapPCDFileASCII needs at least one submap")
+        li = self._layout(*in_layout)
+        arr, keep, residency, _, P = self._submap_table(submaps, poses, int(in_layout[0]))
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        size = C.c_size_t()
+        capi.check(self._lib.lsr_save_map_pcd_ascii(self._h, os.fsencode(path), arr, n, C.byref(li), 1 if residency else 0,
+                                                    P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.byref(size)),
+                   "saveMapPCDFileASCII")
+        return int(size.value)
+
+    def pcdPieceRecords(self, records: Optional[int] = None) -> int:
+        """Records per piece of savePCDFileASCII / saveMapPCDFileASCII (LSR_PCD_PIECE_RECORDS, 64 .. 1 << 22): sets it when given,
+        returns the current value.  The file's bytes do not depend on it."""
+        if records is not None:
+            capi.check(self._lib.lsr_set_i32(self._h, capi.PCD_PIECE_RECORDS, int(records)), "pcdPieceRecords")
+        return self._geti(capi.PCD_PIECE_RECORDS)
 
     def optimizePoseGraph(self, poses, edges, max_iterations: int = 10, band: int = 5):
         """The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319) through lsr_optimize_pose_graph_long: g2o's
