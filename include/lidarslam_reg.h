@@ -121,10 +121,17 @@ typedef enum lsr_key {
   LSR_MAP_ASSEMBLY_FORM = 49,         /* read-only (lsr_get_i32): which form the last lsr_assemble_map on this object took: 0 = none yet,
                                          1 = wide (both layouts {32; 0,4,8,16}, every base pointer 16-byte aligned: two 16-byte loads
                                          and two 16-byte stores per record), 2 = general (any layout).  The bytes are the same */
-  LSR_PCD_PIECE_RECORDS = 50          /* records per piece of lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (64 .. 1 << 22, default 1 << 20): a
+  LSR_PCD_PIECE_RECORDS = 50,         /* records per piece of lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (64 .. 1 << 22, default 1 << 20): a
                                          piece is formatted and copied while the calling thread writes the one before it.  The file's
                                          bytes do not depend on it */
+  LSR_GICP_SOLVER = 51                /* GICP inner optimiser (lsr_gicp_solver): LSR_GICP_GAUSS_NEWTON (default) or LSR_GICP_BFGS, the
+                                         reference's own schedule (PCL's port of GSL vector_bfgs2: Fletcher line search, memoryless
+                                         direction update, |g| < 1e-2 / max_inner_iterations / no progress).  Per object, no environment
+                                         preset; every entry that aligns a GICP object follows it (lsr_align, the batches, lsr_search_loop,
+                                         the frontend paths), and a batch may mix objects with different solvers.  Any other value:
+                                         LSR_ERR_INVALID_ARGUMENT */
 } lsr_key;
+typedef enum lsr_gicp_solver { LSR_GICP_GAUSS_NEWTON = 0 /* default */, LSR_GICP_BFGS = 1 } lsr_gicp_solver;
 /* Environment presets read when an object is created: LSR_NDT_WORKGROUP, LSR_NDT_TABLE_MODE, LSR_NDT_QUAD, LSR_GRID_BUILDER,
  * LSR_WAIT_MODE (the keys above); LSR_NDT_CHAINS=1|2|3 fixes the number of independent launch chains a candidate set runs as (default: two
  * from six members on, each on a stream verified to run concurrently with the object's own; LSR_DEBUG_STREAMS=1 prints what the
@@ -134,11 +141,12 @@ typedef enum lsr_key {
 typedef struct lsr_result {
   int32_t converged;            /* hasConverged()                             scanmatcher_component.cpp:375 */
   int32_t iterations;           /* nr_iterations_ */
-  double score;                 /* NDT: trans_probability_ (= score / N); GICP: final mean Mahalanobis cost */
+  double score;                 /* NDT: trans_probability_ (= score / N); GICP: final mean Mahalanobis cost (either solver) */
   int32_t n_evaluations;        /* NDT: derivative evaluations as the reference counts them (computeDerivatives calls + the
                                    computeHessian after a line search that took trial steps).  The tenth trial of a search
                                    and the computeHessian behind it are ONE launch here and count as two.
-                                   GICP: Gauss-Newton inner steps */
+                                   GICP: Gauss-Newton inner steps; under LSR_GICP_BFGS the cost/gradient passes of the align (every
+                                   pass yields f and g: fewer than the functor calls the reference's wrapper would count) */
   int32_t n_correspondences;    /* GICP: pairs in the last outer iteration; NDT: valid (point, voxel) pairs of the last derivative pass */
   double gpu_ms;                /* HOST wall-clock time of the align call that produced this result, from the first
                                    enqueue to the result in host memory; for lsr_align_batch every member carries the
@@ -626,6 +634,17 @@ int lsr_gicp_covariances(lsr_handle h, int which, double* cov);
  * LSR_ERR_TOO_FEW_POINTS as lsr_align. */
 int lsr_gicp_linearize(lsr_handle h, const float* guess16, const float* trans16, int use_seeds, float* out, int32_t* nn_idx,
                        int32_t* valid, double* M6, float* q, double* x6, float* T12, double* dR27, int32_t* m, double* sums28);
+/* GICP, ONE outer iteration under the BFGS inner optimiser as lsr_align(h, guess16) runs it with LSR_GICP_SOLVER = LSR_GICP_BFGS
+ * (whatever the key says): one correspondence pass at transformation_ = trans16 (col-major; NULL = identity), then that outer
+ * iteration's whole inner loop, by the launches of lsr_align itself; a later lsr_align returns what it would have returned without
+ * the call.  Inspection only (parity tests).  Outputs, each nullable.  Per cost/gradient evaluation e, in order, for the first
+ * `capacity` of them: x6[6 e ..] the point, f[e] the mean cost, g6[6 e ..] the gradient, inner[e] the inner iteration it belonged to
+ * (0 = the evaluation at the start x, k = the line search of the k-th step).  n_evals = evaluations in all (may exceed capacity);
+ * n_inner = steps taken; reason = why the inner loop ended: 1 no progress, 2 gradient tolerance (|g| < 1e-2), 3 max_inner_iterations
+ * reached, 0 left still running (max_inner_iterations < 1: the reference's solver throws), 4 a non-finite cost or gradient;
+ * x6_final = where it ended; m = the pair count (m < 4 returns LSR_OK, m and n_evals = 0).  LSR_ERR_TOO_FEW_POINTS as lsr_align. */
+int lsr_gicp_bfgs_trace(lsr_handle h, const float* guess16, const float* trans16, int32_t capacity, double* x6, double* f, double* g6,
+                        int32_t* inner, int32_t* n_evals, int32_t* n_inner, int32_t* reason, double* x6_final, int32_t* m);
 /* 1-NN of the source transformed by T16 (nullable = identity) in the target: idx[n], d2[n]. */
 int lsr_nearest_neighbors(lsr_handle h, const float* T16, int32_t* idx, float* d2);
 int lsr_get_profile(lsr_handle h, lsr_profile* out, int reset);

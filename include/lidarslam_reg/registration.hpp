@@ -254,6 +254,13 @@ class GeneralizedIterativeClosestPoint : public Registration<PointSource, PointT
   void setRotationEpsilon(double e) { this->check(lsr_set_f64(this->h_, LSR_ROTATION_EPSILON, e), "setRotationEpsilon"); }
   void setCorrespondenceRandomness(int k) { this->check(lsr_set_i32(this->h_, LSR_K_CORRESPONDENCES, k), "setCorrespondenceRandomness"); }
   void setMaximumOptimizerIterations(int n) { this->check(lsr_set_i32(this->h_, LSR_MAX_INNER_ITERATIONS, n), "setMaximumOptimizerIterations"); }
+  // the inner optimiser of align(): LSR_GICP_GAUSS_NEWTON (default) or LSR_GICP_BFGS, the schedule of the class this one replaces
+  void setOptimizer(lsr_gicp_solver s) { this->check(lsr_set_i32(this->h_, LSR_GICP_SOLVER, (int)s), "setOptimizer"); }
+  lsr_gicp_solver getOptimizer() const {
+    int v = 0;
+    this->check(lsr_get_i32(this->h_, LSR_GICP_SOLVER, &v), "getOptimizer");
+    return (lsr_gicp_solver)v;
+  }
 };
 
 }  // namespace lidarslam_reg

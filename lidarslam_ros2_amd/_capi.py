@@ -27,6 +27,8 @@ PCD_ASCII_MAX_LINE_BYTES, PCD_ASCII_MAX_HEADER_BYTES = 60, 256
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
  HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED,
  MAP_ASSEMBLY_FORM) = range(32, 50)
+GICP_SOLVER = 51
+GICP_GAUSS_NEWTON, GICP_BFGS = 0, 1
 
 EXPORTED_SYMBOLS = [
     "lsr_version", "lsr_status_string", "lsr_last_error", "lsr_device_count", "lsr_create", "lsr_destroy",
@@ -41,7 +43,7 @@ EXPORTED_SYMBOLS = [
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
     "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
     "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long",
-    "lsr_format_pcd_ascii", "lsr_save_pcd_ascii", "lsr_save_map_pcd_ascii",
+    "lsr_format_pcd_ascii", "lsr_save_pcd_ascii", "lsr_save_map_pcd_ascii", "lsr_gicp_bfgs_trace",
 ]
 
 
@@ -178,6 +180,7 @@ def load() -> C.CDLL:
     L.lsr_gicp_covariances.argtypes = [vp, C.c_int, dp]
     L.lsr_nearest_neighbors.argtypes = [vp, fp, ip, fp]
     L.lsr_gicp_linearize.argtypes = [vp, fp, fp, C.c_int, fp, ip, ip, dp, fp, dp, fp, dp, ip, dp]
+    L.lsr_gicp_bfgs_trace.argtypes = [vp, fp, fp, C.c_int32, dp, dp, dp, ip, ip, ip, ip, dp, ip]
     L.lsr_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
     L.lsr_debug_angle_tables.argtypes = [dp, C.c_int, fp, fp, fp, fp]
     L.lsr_set_input_source_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_double, C.c_float, C.c_int,

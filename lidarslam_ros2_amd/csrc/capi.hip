@@ -946,6 +946,9 @@ int lsr_set_i32(lsr_handle h, int key, int v) {
       if (v < 3 || v > GICP_MAX_K) { set_last_error("k_correspondences out of range"); return LSR_ERR_INVALID_ARGUMENT; }
       h->gicp.k = v; h->source_cov_valid = false; if (h->target) h->target->has_cov = false; return LSR_OK;
     case LSR_MAX_INNER_ITERATIONS: h->gicp.max_inner = v; return LSR_OK;
+    case LSR_GICP_SOLVER:
+      if (v != LSR_GICP_GAUSS_NEWTON && v != LSR_GICP_BFGS) { set_last_error("unknown GICP solver"); return LSR_ERR_INVALID_ARGUMENT; }
+      h->gicp.solver = v; return LSR_OK;
     case LSR_RANSAC_ITERATIONS: h->ransac_iterations = v; return LSR_OK;  // no effect on NDT/GICP maths
     case LSR_HESSIAN_D1_SIGN: h->ndt.d1_sign = (v >= 0) ? 1 : -1; return LSR_OK;
     case LSR_PROFILE: h->profile = v ? 1 : 0; return LSR_OK;
@@ -990,6 +993,7 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_NUM_THREADS: *v = h->num_threads; return LSR_OK;
     case LSR_K_CORRESPONDENCES: *v = h->gicp.k; return LSR_OK;
     case LSR_MAX_INNER_ITERATIONS: *v = h->gicp.max_inner; return LSR_OK;
+    case LSR_GICP_SOLVER: *v = h->gicp.solver; return LSR_OK;
     case LSR_RANSAC_ITERATIONS: *v = h->ransac_iterations; return LSR_OK;
     case LSR_HESSIAN_D1_SIGN: *v = h->ndt.d1_sign; return LSR_OK;
     case LSR_PROFILE: *v = h->profile; return LSR_OK;
@@ -2442,6 +2446,15 @@ int lsr_gicp_linearize(lsr_handle h, const float* guess16, const float* trans16,
   if (h->method != LSR_METHOD_GICP) { set_last_error("lsr_gicp_linearize on an NDT object"); return LSR_ERR_INVALID_ARGUMENT; }
   const GicpLinearizeOut o{out, nn_idx, valid, M6, q, x6, T12, dR27, m, sums28};
   return gicp_linearize(h, guess16, trans16, use_seeds, o);
+}
+
+int lsr_gicp_bfgs_trace(lsr_handle h, const float* guess16, const float* trans16, int32_t capacity, double* x6, double* f, double* g6,
+                        int32_t* inner, int32_t* n_evals, int32_t* n_inner, int32_t* reason, double* x6_final, int32_t* m) {
+  LSR_CHECK_HANDLE(h);
+  if (h->method != LSR_METHOD_GICP) { set_last_error("lsr_gicp_bfgs_trace on an NDT object"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (capacity < 0) { set_last_error("capacity must be >= 0"); return LSR_ERR_INVALID_ARGUMENT; }
+  const GicpBfgsTraceOut o{x6, f, g6, inner, n_evals, n_inner, reason, x6_final, m};
+  return gicp_bfgs_trace(h, guess16, trans16, capacity, o);
 }
 
 int lsr_get_profile(lsr_handle h, lsr_profile* out, int reset) {

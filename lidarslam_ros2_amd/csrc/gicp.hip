@@ -8,14 +8,20 @@
 //   K7  gicp_step_kernel          one Gauss-Newton step per launch: consumes the partial rows of the previous step (fixed-order
 //                                 sum, gradient test, 6x6 solve on a wave, state update, the reference's outer bookkeeping),
 //                                 then accumulates 28 fp64 sums (cost, 6-gradient, 21-Hessian) at the new state
+//   K7b gicp_bfgs_step_kernel     (LSR_GICP_SOLVER = LSR_GICP_BFGS) one cost/gradient evaluation of the reference's BFGS inner
+//                                 optimiser per launch: consumes the partial rows of the previous evaluation (fixed-order sum,
+//                                 f and g from 13 sums, the automaton of gicp_bfgs.hpp on one lane, the same outer bookkeeping),
+//                                 then accumulates 13 fp64 sums (cost, sum M r, sum p (M r)^T) at the x the automaton asks for
 // The whole outer loop runs on the device; the host (GicpChain) keeps launches queued — one K6 launch followed by a few K7
 // launches, again and again — and polls a mailbox.
-// The reference minimises the same cost with BFGS; north_star asks for Gauss-Newton accumulation, so
-// the inner solver here is GN with the reference's stopping rule (|grad| < 1e-2 or max_inner
-// iterations).  Same cost and correspondences => same minimiser; the oracle carries both solvers.
+// The reference minimises the cost with BFGS (PCL's port of GSL vector_bfgs2); north_star asks for Gauss-Newton accumulation, so
+// the DEFAULT inner solver here is GN with the reference's stopping rule (|grad| < 1e-2 or max_inner iterations): same cost and
+// correspondences => same minimiser.  An object set to LSR_GICP_BFGS follows the reference's own schedule instead — line search,
+// memoryless direction update, stopping rules and all (gicp_bfgs.hpp) — at several times the passes; the oracle carries both.
 #include <chrono>
 #include <thread>
 
+#include "gicp_bfgs.hpp"
 #include "handle.hpp"
 #include "nn_device.hpp"
 
@@ -35,6 +41,8 @@ constexpr int GN_THREADS = 256;
 // that adopts a count remembers the total): 7 500 waves adding to ONE address took 100 us, 13 ns per atomic.
 constexpr int GICP_COUNT_SHARDS = 64, GICP_SHARD_STRIDE = 16;
 constexpr int GN_NRED = 28;  // [0] cost, [1..6] J^T M r, [7..27] upper triangle of J^T M J
+constexpr int BF_NRED = 13;  // the BFGS pass: [0] cost, [1..3] sum M r, [4..12] sum p (M r)^T row by row
+constexpr int BF_TRACE_WORDS = 14;   // lsr_gicp_bfgs_trace, one record per evaluation: x[6], f, g[6], inner iteration
 
 struct PairRec {      // one candidate correspondence, written by K6, streamed by K7
   float q[3];         // target point
@@ -82,6 +90,7 @@ struct IterBlock {    // uploaded once per align
   int have_partials;  // the previous step left partial rows at the current x (to be consumed by the next step)
   int count_base;     // sharded pair counters (GICP_COUNT_SHARDS): their total when the previous outer iteration adopted it
   int pad;
+  BfgsState bf;       // LSR_GICP_BFGS: the inner optimiser between two evaluations (gicp_bfgs.hpp); untouched by Gauss-Newton
 };
 
 // f6 = {cos a, sin a, cos b, sin b, cos c, sin c} of the FLOAT angles, d6 = the same of the double angles (x[3..5])
@@ -495,41 +504,13 @@ __host__ __device__ inline void gicp_begin_outer(IterBlock& B) {
   gn_apply_state(B.st);
 }
 
-// ---- Gauss-Newton chain ("pull", as the NDT chain): step s first consumes what step s-1 accumulated — every
-// workgroup, redundantly and deterministically, on an LDS copy of the iteration block: fixed-order sum of the partial rows,
-// gradient test, 6x6 solve, state update, and at the end of an inner loop the reference's outer bookkeeping — then
-// accumulates its share of the pairs at the NEW state.  One launch per inner iteration, no single-workgroup launch on the
-// critical path.  The block is double buffered by step parity (step s reads blk[s & 1], workgroup 0 writes blk[(s + 1) & 1]);
-// the correspondence launch between steps s-1 and s works on blk[s & 1].
-// gicp_advance is the bookkeeping of one step on one lane.  Returns bit 0: this launch has pairs to accumulate at the state it
-// leaves in Bk; bit 1: that state's x is new and needs its trigonometry.  When the inner loop goes on it raises *need_solve and
-// returns -1 instead: the caller solves on the wave (solve6_gn_wave), moves x and takes 1 | 2 as the code.
-__device__ int gicp_advance(IterBlock& Bk, const double* s_sum, GicpMailbox* mb, unsigned int token, bool publish, int* need_solve) {
+// The inner loop of an outer iteration has ended (either solver; S->x is where it ended, S->T composed from it, S->f / S->gnorm /
+// S->inner_iter what it reports): the reference's outer bookkeeping — transformation_ from x, the delta stop rule,
+// nr_iterations, the next Mahalanobis rotation, the mailbox.  Returns 0 (the align is over) or 2 (the next outer iteration's start x
+// needs its trigonometry).
+__device__ int gicp_end_inner(IterBlock& Bk, GicpMailbox* mb, unsigned int token, bool publish) {
   GnState* S = &Bk.st;
   OuterState* O = &Bk.out;
-  if (!Bk.have_partials) {
-    // first step of this outer iteration: the correspondence pass has just run, adopt its pair count
-    O->phase = O->phase + 1;
-    S->m = Bk.count;
-    if (S->m >= 4) {   // (fewer: the reference's NotEnoughPointsException — x is left alone, the outer loop ends below)
-      Bk.have_partials = 1;
-      return 1;         // evaluate at the start x
-    }
-  } else {
-    const double m = (double)S->m;
-    double g[6];
-    S->f = s_sum[0] / m;
-    for (int k = 0; k < 6; k++) g[k] = 2.0 * s_sum[1 + k] / m;
-    double gn = 0;
-    for (int k = 0; k < 6; k++) gn += g[k] * g[k];
-    gn = sqrt(gn);
-    S->gnorm = gn;
-    if (!(gn < 1e-2 || S->inner_iter >= S->max_inner || !(gn == gn))) {  // else BFGS testGradient(1e-2) / max_inner_iterations_: loop over
-      *need_solve = 1;   // the wave forms H itself (solve6_gn_wave): 21 fp64 divisions less on this lane
-      return -1;
-    }
-  }
-  // ---- the inner loop of this outer iteration has ended: the reference's outer bookkeeping
   Bk.have_partials = 0;
   bool stop = false;
   O->last_cnt = S->m;
@@ -579,6 +560,43 @@ __device__ int gicp_advance(IterBlock& Bk, const double* s_sum, GicpMailbox* mb,
   gicp_begin_outer_pre(Bk);
   O->phase = (O->phase | 1) + 1;  // next even phase: the correspondence pass of the next outer iteration
   return 2;                       // nothing to accumulate, but the new start x needs its trigonometry
+}
+
+// ---- Gauss-Newton chain ("pull", as the NDT chain): step s first consumes what step s-1 accumulated — every
+// workgroup, redundantly and deterministically, on an LDS copy of the iteration block: fixed-order sum of the partial rows,
+// gradient test, 6x6 solve, state update, and at the end of an inner loop the reference's outer bookkeeping — then
+// accumulates its share of the pairs at the NEW state.  One launch per inner iteration, no single-workgroup launch on the
+// critical path.  The block is double buffered by step parity (step s reads blk[s & 1], workgroup 0 writes blk[(s + 1) & 1]);
+// the correspondence launch between steps s-1 and s works on blk[s & 1].
+// gicp_advance is the bookkeeping of one step on one lane.  Returns bit 0: this launch has pairs to accumulate at the state it
+// leaves in Bk; bit 1: that state's x is new and needs its trigonometry.  When the inner loop goes on it raises *need_solve and
+// returns -1 instead: the caller solves on the wave (solve6_gn_wave), moves x and takes 1 | 2 as the code.
+__device__ int gicp_advance(IterBlock& Bk, const double* s_sum, GicpMailbox* mb, unsigned int token, bool publish, int* need_solve) {
+  GnState* S = &Bk.st;
+  OuterState* O = &Bk.out;
+  if (!Bk.have_partials) {
+    // first step of this outer iteration: the correspondence pass has just run, adopt its pair count
+    O->phase = O->phase + 1;
+    S->m = Bk.count;
+    if (S->m >= 4) {   // (fewer: the reference's NotEnoughPointsException — x is left alone, the outer loop ends below)
+      Bk.have_partials = 1;
+      return 1;         // evaluate at the start x
+    }
+  } else {
+    const double m = (double)S->m;
+    double g[6];
+    S->f = s_sum[0] / m;
+    for (int k = 0; k < 6; k++) g[k] = 2.0 * s_sum[1 + k] / m;
+    double gn = 0;
+    for (int k = 0; k < 6; k++) gn += g[k] * g[k];
+    gn = sqrt(gn);
+    S->gnorm = gn;
+    if (!(gn < 1e-2 || S->inner_iter >= S->max_inner || !(gn == gn))) {  // else BFGS testGradient(1e-2) / max_inner_iterations_: loop over
+      *need_solve = 1;   // the wave forms H itself (solve6_gn_wave): 21 fp64 divisions less on this lane
+      return -1;
+    }
+  }
+  return gicp_end_inner(Bk, mb, token, publish);
 }
 
 __global__ __launch_bounds__(GN_THREADS) void gicp_step_kernel(IterBlock* __restrict__ blk2, int step, const float* __restrict__ ox,
@@ -736,6 +754,189 @@ __global__ __launch_bounds__(GN_THREADS) void gicp_step_kernel(IterBlock* __rest
   }
 }
 
+// ---- BFGS chain (LSR_GICP_BFGS): the same pull chain with the reference's own inner optimiser.  Launch s consumes the 13 sums launch
+// s-1 accumulated — f and g of ONE evaluation (bfgs_cost_gradient) — hands them to the automaton (gicp_bfgs.hpp: bfgs_consume), which
+// either asks for the next evaluation point or reports the inner loop finished; then accumulates at the point asked for.  One
+// evaluation per launch; a line search is as many launches as it takes trials.  Every pass yields f AND g (the wrapper the
+// reference runs sometimes asks for f alone): the same values, since a pass is a fixed-order sum and so a function of x alone —
+// only the number of passes differs from the reference's number of functor calls.
+// gicp_bfgs_advance: the bookkeeping of one launch on one lane; the return code is gicp_advance's (bit 0 accumulate, bit 1 new x).
+__device__ int gicp_bfgs_advance(IterBlock& Bk, const double* s_sum, GicpMailbox* mb, unsigned int token, bool publish,
+                                 double* __restrict__ trace, int trace_cap) {
+  GnState* S = &Bk.st;
+  OuterState* O = &Bk.out;
+  BfgsState& F = Bk.bf;
+  if (!Bk.have_partials) {
+    // first launch of this outer iteration: the correspondence pass has just run, adopt its pair count
+    O->phase = O->phase + 1;
+    S->m = Bk.count;
+    if (S->m >= 4) {   // (fewer: the reference's NotEnoughPointsException — x is left alone, the outer loop ends below)
+      Bk.have_partials = 1;
+      bfgs_begin(F, S->x, S->max_inner);
+      return 1;         // Bfgs::init: evaluate at the start x
+    }
+  } else {
+    double f, g[6];
+    bfgs_cost_gradient(s_sum, S->m, S->dR, &f, g);
+    if (trace && publish && F.n_evals < trace_cap) {   // lsr_gicp_bfgs_trace
+      double* rec = trace + (size_t)F.n_evals * BF_TRACE_WORDS;
+      for (int k = 0; k < 6; k++) { rec[k] = S->x[k]; rec[7 + k] = g[k]; }
+      rec[6] = f;
+      rec[13] = (double)F.inner;
+    }
+    if (bfgs_consume(F, f, g) == BFGS_EVAL) {
+      for (int k = 0; k < 6; k++) S->x[k] = F.x_req[k];
+      return 1 | 2;     // evaluate at the x asked for, whose trigonometry is spread over lanes by the caller
+    }
+    // the inner loop is over at x0, the last accepted point — not always the last one evaluated (a line search that ends without
+    // progress): transformation_ is composed from it here
+    for (int k = 0; k < 6; k++) S->x[k] = F.x0[k];
+    gn_apply_state(*S);
+    S->f = F.f;
+    // a solver that failed (non-finite values; the driver's loop left while still running) takes the NaN exit of the bookkeeping
+    S->gnorm = bfgs_accepted(F) ? bfgs_detail::nrm6(F.g0) : bfgs_detail::quiet_nan();
+    S->inner_iter = F.n_evals;   // lsr_result.n_evaluations counts cost/gradient passes
+  }
+  return gicp_end_inner(Bk, mb, token, publish);
+}
+
+// The BF_NRED sums of one wave through its LDS tile (wave_sums_tile's shape, one round of thirteen rows)
+constexpr int BF_TILE_ROWS = BF_NRED;
+__device__ __forceinline__ void wave_sums_tile13(const double* acc, double* tile, double* out, const int lane) {
+#pragma unroll
+  for (int k = 0; k < BF_TILE_ROWS; k++) tile[k * GN_TILE_PITCH + lane] = acc[k];
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  if (lane < 2 * BF_TILE_ROWS) {
+    const int k = lane >> 1, h = lane & 1;
+    const double* row = tile + k * GN_TILE_PITCH + 32 * h;
+    double v = row[0];
+#pragma unroll
+    for (int j = 1; j < 32; j++) v += row[j];
+    const double other = __shfl_xor(v, 1, 64);
+    if (h == 0) out[k] = v + other;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(GN_THREADS) void gicp_bfgs_step_kernel(IterBlock* __restrict__ blk2, int step, const float* __restrict__ ox,
+                                                                    const float* __restrict__ oy, const float* __restrict__ oz, int n,
+                                                                    const PairRec* __restrict__ pairs, double* __restrict__ partials2,
+                                                                    int nblocks, GicpMailbox* mb, unsigned int token, int launch_index,
+                                                                    const int* __restrict__ count_shards,
+                                                                    double* __restrict__ trace /* nullable: inspection */, int trace_cap) {
+  __shared__ __attribute__((aligned(16))) unsigned long long s_raw[sizeof(IterBlock) / 8];
+  __shared__ double s_grp[8][32];
+  __shared__ double s_sum[32];
+  __shared__ double s_red[GN_THREADS / 64][BF_NRED];
+  __shared__ double s_tile[GN_THREADS / 64][BF_TILE_ROWS * GN_TILE_PITCH];
+  __shared__ int s_do;
+  IterBlock& Bk = *reinterpret_cast<IterBlock*>(s_raw);
+  const int t = threadIdx.x;
+  constexpr int NW = (int)(sizeof(IterBlock) / 8);
+  {
+    const unsigned long long* in = reinterpret_cast<const unsigned long long*>(blk2 + (step & 1));
+    for (int w = t; w < NW; w += GN_THREADS) s_raw[w] = in[w];
+  }
+  __syncthreads();
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(blk2 + ((step + 1) & 1));
+  const unsigned long long progress = ((unsigned long long)token << 32) | (unsigned int)launch_index;
+  const int ph = Bk.out.phase;
+  if (Bk.out.outer_done || (!(ph & 1) && Bk.out.corr_mark != ph)) {  // all over, or no fresh pairs yet: carry the block forward
+    if (blockIdx.x == 0) {
+      for (int w = t; w < NW; w += GN_THREADS) out[w] = s_raw[w];
+      if (t == 0) __hip_atomic_store(&mb->progress, progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return;
+  }
+  if (Bk.have_partials) {   // rows the previous launch left in the other bank: 8 groups x 32 values, fixed order
+    const double* rows = partials2 + (size_t)((step + 1) & 1) * nblocks * 32;
+    const int v = t & 31, grp = t >> 5;
+    double acc = 0.0;
+    if (v < BF_NRED)
+      for (int b = grp; b < nblocks; b += 8) acc += rows[(size_t)b * 32 + v];
+    s_grp[grp][v] = acc;
+    __syncthreads();
+    if (t < 32) {
+      double v2 = 0.0;
+      for (int g2 = 0; g2 < 8; g2++) v2 += s_grp[g2][t];
+      s_sum[t] = v2;
+    }
+  }
+  __syncthreads();
+  __shared__ float s_f6[6];
+  __shared__ double s_d6[6];
+  if (t < 64) {   // wave 0: the pair count on the wave, the automaton and the bookkeeping on lane 0
+    if (!Bk.have_partials) {   // the correspondence pass has just run: its pair count = the counters' total - the last one
+      int total = count_shards[t * GICP_SHARD_STRIDE];
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) total += __shfl_xor(total, m, 64);
+      if (t == 0) { Bk.count = total - Bk.count_base; Bk.count_base = total; }
+    }
+    if (t == 0) s_do = gicp_bfgs_advance(Bk, s_sum, mb, token, blockIdx.x == 0, trace, trace_cap);
+  }
+  __syncthreads();
+  if (s_do & 2) {   // sin/cos of the three angles: fp32 on lanes 0..2 of wave 0, fp64 on lanes 0..2 of wave 1, side by side
+    if (t < 3) {
+      const float ang = (float)Bk.st.x[3 + t];
+      s_f6[2 * t] = cosf(ang);
+      s_f6[2 * t + 1] = sinf(ang);
+    } else if (t >= 64 && t < 67) {
+      const double ang = Bk.st.x[3 + (t - 64)];
+      s_d6[2 * (t - 64)] = cos(ang);
+      s_d6[2 * (t - 64) + 1] = sin(ang);
+    }
+    __syncthreads();
+    if (t == 0) gn_apply_state_trig(Bk.st, s_f6, s_d6);
+    __syncthreads();
+  }
+  if (blockIdx.x == 0) {
+    for (int w = t; w < NW; w += GN_THREADS) out[w] = s_raw[w];
+    if (t == 0) __hip_atomic_store(&mb->progress, progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (!(s_do & 1)) return;
+  // ---- one evaluation of the reference's functor at the state just left in Bk: no Jacobian, no Hessian
+  const GnState* S = &Bk.st;
+  float T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = S->T[k];
+  double acc[BF_NRED];
+#pragma unroll
+  for (int k = 0; k < BF_NRED; k++) acc[k] = 0.0;
+  for (int i = blockIdx.x * GN_THREADS + threadIdx.x; i < n; i += gridDim.x * GN_THREADS) {
+    const PairRec r = pairs[i];
+    if (!r.valid) continue;
+    const float a = ox[i], b = oy[i], c = oz[i];
+    // transformation_matrix * p_src in float, residual promoted to double (OptimizationFunctorWithIndices)
+    const float ppx = xform_rn(T[0], T[1], T[2], T[3], a, b, c);
+    const float ppy = xform_rn(T[4], T[5], T[6], T[7], a, b, c);
+    const float ppz = xform_rn(T[8], T[9], T[10], T[11], a, b, c);
+    const double res[3] = {(double)(ppx - r.q[0]), (double)(ppy - r.q[1]), (double)(ppz - r.q[2])};
+    const double p[3] = {(double)a, (double)b, (double)c};
+    const double M00 = r.M[0], M01 = r.M[1], M02 = r.M[2], M11 = r.M[3], M12 = r.M[4], M22 = r.M[5];
+    const double Mr0 = M00 * res[0] + M01 * res[1] + M02 * res[2];
+    const double Mr1 = M01 * res[0] + M11 * res[1] + M12 * res[2];
+    const double Mr2 = M02 * res[0] + M12 * res[1] + M22 * res[2];
+    acc[0] += res[0] * Mr0 + res[1] * Mr1 + res[2] * Mr2;
+    acc[1] += Mr0; acc[2] += Mr1; acc[3] += Mr2;
+#pragma unroll
+    for (int u = 0; u < 3; u++) {   // p (M r)^T: contracted with dR by the consuming launch (the reference's tr(dR_k * R))
+      acc[4 + 3 * u] += p[u] * Mr0;
+      acc[5 + 3 * u] += p[u] * Mr1;
+      acc[6 + 3 * u] += p[u] * Mr2;
+    }
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  wave_sums_tile13(acc, s_tile[wid], s_red[wid], lane);
+  __syncthreads();
+  if (threadIdx.x < BF_NRED) {
+    double v = s_red[0][threadIdx.x];
+    for (int w = 1; w < GN_THREADS / 64; w++) v += s_red[w][threadIdx.x];
+    partials2[(size_t)(step & 1) * nblocks * 32 + (size_t)blockIdx.x * 32 + threadIdx.x] = v;
+  }
+}
+
 int compute_covariances(lsr_handle_s* h, const DeviceCloud& cloud, const HashGridDev& grid, DevBuf<double>& cov, bool raw = false) {
   const int n = (int)cloud.n;
   const double eps = raw ? -1.0 : h->gicp.gicp_eps;
@@ -856,13 +1057,17 @@ struct GicpChain {
   int* d_shards = nullptr;
   double* d_partials = nullptr;
   double* d_sums = nullptr;   // lsr_gicp_linearize only: where the consuming step leaves the reduced sums
+  bool bfgs = false;          // the object's LSR_GICP_SOLVER: which step kernel the groups launch
+  double* d_trace = nullptr;  // lsr_gicp_bfgs_trace only: one record per evaluation
+  int trace_cap = 0;
+  int group_steps = 3;        // step launches per group the queue is topped up with
   IterBlock* d_blk = nullptr;
   PairRec* d_pairs = nullptr;
   long hard_cap = 0;
   unsigned long long last_progress = 0;
   std::chrono::steady_clock::time_point t_begin, t_progress;
 
-  // one correspondence pass on the block the next step will read, then `steps` Gauss-Newton steps
+  // one correspondence pass on the block the next step will read, then `steps` Gauss-Newton steps (BFGS evaluations)
   void enqueue_group(int steps) {
     GicpWorkspace& ws = h->gicp_ws;
     const TargetData& t = *h->target;
@@ -871,8 +1076,12 @@ struct GicpChain {
                        ws.out.x(), ws.out.y(), ws.out.z(), n, cur->T16, cur->Rm, thr2, t.cloud.x(), t.cloud.y(), t.cloud.z(),
                        h->source_cov.p, t.cov.p, &cur->out, ws.last_nn.p, ws.nn_d2.p, d_pairs, d_shards, GICP_BALL_CELLS);
     for (int it = 0; it < steps; it++) {
-      hipLaunchKernelGGL(gicp_step_kernel, dim3(nblocks), dim3(GN_THREADS), 0, s, d_blk, updates, ws.out.x(), ws.out.y(), ws.out.z(), n,
-                         d_pairs, d_partials, nblocks, ws.d_mailbox, token, updates + 1, (const int*)d_shards, d_sums);
+      if (bfgs)
+        hipLaunchKernelGGL(gicp_bfgs_step_kernel, dim3(nblocks), dim3(GN_THREADS), 0, s, d_blk, updates, ws.out.x(), ws.out.y(), ws.out.z(),
+                           n, d_pairs, d_partials, nblocks, ws.d_mailbox, token, updates + 1, (const int*)d_shards, d_trace, trace_cap);
+      else
+        hipLaunchKernelGGL(gicp_step_kernel, dim3(nblocks), dim3(GN_THREADS), 0, s, d_blk, updates, ws.out.x(), ws.out.y(), ws.out.z(), n,
+                           d_pairs, d_partials, nblocks, ws.d_mailbox, token, updates + 1, (const int*)d_shards, d_sums);
       updates++;
     }
   }
@@ -880,8 +1089,11 @@ struct GicpChain {
   // everything up to the first three groups of launches.
   // lin (lsr_gicp_linearize): the same start with transformation_ = lin->trans, then ONE correspondence pass and the accumulation at
   // the start x of that outer iteration, consumed by a step that cannot move x (max_inner = 0) and ends the align (max_iterations = 1).
+  // trace (lsr_gicp_bfgs_trace): the same start with transformation_ = trace->trans, then ONE whole outer iteration (max_iterations = 1)
+  // under the BFGS kernel whatever the object's solver, every evaluation recorded.
   struct Linearize { const float* trans; bool use_seeds; };
-  int begin(lsr_handle_s* handle, const float* guess, const Linearize* lin = nullptr) {
+  struct Trace { const float* trans; int capacity; };
+  int begin(lsr_handle_s* handle, const float* guess, const Linearize* lin = nullptr, const Trace* trace = nullptr) {
     h = handle;
     if (!h->target || h->target->n == 0) { set_last_error("align before setInputTarget"); return LSR_ERR_NO_TARGET; }
     if (!h->has_source) { set_last_error("align before setInputSource"); return LSR_ERR_NO_SOURCE; }
@@ -907,6 +1119,14 @@ struct GicpChain {
     if ((st = ws.pin.reserve(sizeof(IterBlock) + 64))) return st;
     d_partials = ws.buf.p;
     d_sums = lin ? ws.buf.p + (size_t)2 * nblocks * 32 : nullptr;   // the 64 doubles behind the two banks
+    bfgs = !lin && (trace || h->gicp.solver == LSR_GICP_BFGS);
+    d_trace = nullptr;
+    trace_cap = 0;
+    if (trace) {
+      trace_cap = std::max(trace->capacity, 0);
+      if ((st = ws.trace.reserve((size_t)std::max(trace_cap, 1) * BF_TRACE_WORDS))) return st;
+      d_trace = ws.trace.p;
+    }
     d_blk = reinterpret_cast<IterBlock*>(ws.state.p);
     d_pairs = reinterpret_cast<PairRec*>(ws.pairs.p);
 
@@ -937,6 +1157,10 @@ struct GicpChain {
       O.max_iterations = 1;
       hb->st.max_inner = 0;
       O.phase = seeds ? 2 : 0;   // an outer iteration after the first: last_nn is offered as seeds
+    }
+    if (trace) {
+      if (trace->trans) std::memcpy(O.trans, trace->trans, sizeof(I16));
+      O.max_iterations = 1;
     }
     gicp_begin_outer(*hb);
     thr2 = (float)(h->gicp.max_corr_dist * h->gicp.max_corr_dist);
@@ -970,11 +1194,26 @@ struct GicpChain {
     }
     // the first outer iteration typically needs 3-4 Gauss-Newton steps, later ones one or two, and every outer iteration one
     // step more (the step that finds the loop finished accumulates nothing)
-    enqueue_group(5);
-    enqueue_group(3);
-    enqueue_group(3);
+    if (!bfgs) {
+      group_steps = 3;
+      enqueue_group(5);
+      enqueue_group(3);
+      enqueue_group(3);
+      hard_cap = (long)(h->gicp.max_iterations + 2) * (h->gicp.max_inner + 2) + 16;  // step launches an align can need
+    } else {
+      // BFGS: an outer iteration is one evaluation per line-search trial — tens of them in the first outer iteration, a handful in
+      // the later ones — so the groups are longer: the launches of a group behind the end of an inner loop exit at their gate until
+      // the next group's correspondence pass has run (<= group_steps - 1 gated heads per outer iteration), and an inner loop longer
+      // than a group lets the correspondence launches in between exit at theirs.
+      group_steps = 8;
+      enqueue_group(group_steps);
+      enqueue_group(group_steps);
+      enqueue_group(group_steps);
+      // every inner iteration: a line search of <= 100 trials + update_position's evaluation; per outer iteration Bfgs::init, the
+      // launch that finds the loop over, and the gated rest of a group
+      hard_cap = (long)(h->gicp.max_iterations + 2) * ((long)std::max(h->gicp.max_inner, 1) * (BFGS_LINE_ITERS + 1) + 2 + group_steps) + 16;
+    }
     LSR_HIP(hipGetLastError());
-    hard_cap = (long)(h->gicp.max_iterations + 2) * (h->gicp.max_inner + 2) + 16;  // step launches an align can need
     last_progress = 0;
     t_progress = std::chrono::steady_clock::now();
     done = false;
@@ -987,10 +1226,10 @@ struct GicpChain {
     if (__atomic_load_n(&mb->done, __ATOMIC_ACQUIRE) == token) { done = true; return LSR_OK; }
     const unsigned long long pr = __atomic_load_n(&mb->progress, __ATOMIC_RELAXED);
     const int ran = ((unsigned int)(pr >> 32) == token) ? (int)(unsigned int)pr : 0;
-    if (updates - ran < 5) {  // fewer than two groups left in the queue: top up
+    if (updates - ran < 2 * group_steps - 1) {  // fewer than two groups left in the queue: top up
       if (updates > hard_cap) { set_last_error("GICP launch chain did not finish within its launch cap"); return LSR_ERR_HIP; }
-      enqueue_group(3);
-      enqueue_group(3);
+      enqueue_group(group_steps);
+      enqueue_group(group_steps);
       LSR_HIP(hipGetLastError());
       return LSR_OK;
     }
@@ -1079,6 +1318,43 @@ int gicp_linearize(lsr_handle_s* h, const float* guess, const float* trans, int 
   if (o.dR27) for (int k = 0; k < 27; k++) o.dR27[k] = blk.st.dR[k];
   if (o.m) *o.m = blk.st.m;
   if (o.sums28) for (int k = 0; k < GN_NRED; k++) o.sums28[k] = sums[k];
+  return LSR_OK;
+}
+
+// lsr_gicp_bfgs_trace: ONE outer iteration whose transformation_ is `trans` — its correspondence pass and its whole BFGS inner loop — by
+// the launches of gicp_align under LSR_GICP_BFGS, every evaluation recorded by the launch that consumes it.  The object's result
+// (final transformation, converged) is left alone.
+int gicp_bfgs_trace(lsr_handle_s* h, const float* guess, const float* trans, int capacity, const GicpBfgsTraceOut& o) {
+  GicpChain c;
+  const GicpChain::Trace tr{trans, capacity};
+  int st = c.begin(h, guess, nullptr, &tr);
+  if (st) return st;
+  for (unsigned long long spins = 1; !c.done; spins++) {
+    if ((st = c.poll(spins))) return st;
+    if (!c.done) wait_between_polls(h->scratch.wait_mode);
+  }
+  IterBlock blk;
+  const IterBlock* d_final = c.d_blk + (c.updates & 1);   // launch s leaves the block in bank (s + 1) & 1
+  const int cap = c.trace_cap;
+  std::vector<double> rec((size_t)std::max(cap, 1) * BF_TRACE_WORDS);
+  LSR_HIP(hipMemcpyAsync(&blk, d_final, sizeof(IterBlock), hipMemcpyDeviceToHost, c.s));
+  if (cap > 0) LSR_HIP(hipMemcpyAsync(rec.data(), c.d_trace, sizeof(double) * BF_TRACE_WORDS * cap, hipMemcpyDeviceToHost, c.s));
+  LSR_HIP(hipStreamSynchronize(c.s));
+  if (!blk.out.outer_done) { set_last_error("GICP BFGS trace: the launch chain did not reach its end"); return LSR_ERR_HIP; }
+  const BfgsState& F = blk.bf;
+  const int got = std::min(F.n_evals, cap);
+  for (int e = 0; e < got; e++) {
+    const double* r = rec.data() + (size_t)e * BF_TRACE_WORDS;
+    if (o.x6) for (int k = 0; k < 6; k++) o.x6[6 * e + k] = r[k];
+    if (o.f) o.f[e] = r[6];
+    if (o.g6) for (int k = 0; k < 6; k++) o.g6[6 * e + k] = r[7 + k];
+    if (o.inner) o.inner[e] = (int)r[13];
+  }
+  if (o.n_evals) *o.n_evals = F.n_evals;
+  if (o.n_inner) *o.n_inner = F.inner;
+  if (o.reason) *o.reason = F.reason;
+  if (o.x6_final) for (int k = 0; k < 6; k++) o.x6_final[k] = blk.st.x[k];
+  if (o.m) *o.m = blk.st.m;
   return LSR_OK;
 }
 

@@ -15,6 +15,7 @@ struct GicpParamsHost {
   int max_iterations = 200;
   int max_inner = 20;
   int k = 20;
+  int solver = 0;                 // LSR_GICP_SOLVER: LSR_GICP_GAUSS_NEWTON (default) / LSR_GICP_BFGS
 };
 
 // Host mailbox of a GICP align (pinned, host-coherent, mapped into the device): the launch chain reports how many of
@@ -39,6 +40,7 @@ struct GicpWorkspace {
   DevBuf<int> last_nn;           // K6: each source point's neighbour in the previous outer iteration (search seed)
   DevBuf<float> nn_d2;           // K6: its squared distance
   DevBuf<int> count_shards;      // K6: pair counters of the correspondence pass, a cache line apart
+  DevBuf<double> trace;          // lsr_gicp_bfgs_trace only: one record per evaluation
   PinBuf<GicpMailbox> mailbox;
   GicpMailbox* d_mailbox = nullptr;
   unsigned int token = 0;        // one per align
@@ -52,11 +54,17 @@ struct GicpLinearizeOut {
   float* out; int* nn_idx; int* valid; double* M6; float* q; double* x6; float* T12; double* dR27; int* m; double* sums28;
 };
 
+// lsr_gicp_bfgs_trace's outputs (include/lidarslam_reg.h), each nullable
+struct GicpBfgsTraceOut {
+  double* x6; double* f; double* g6; int* inner; int* n_evals; int* n_inner; int* reason; double* x6_final; int* m;
+};
+
 int gicp_align(lsr_handle_s* h, const float* guess, float* final_T, lsr_result* res);
 // B registrations side by side (each chain on its own object's stream, one host loop feeding them all)
 int gicp_align_batch(lsr_handle_s* const* hs, int B, const float* guesses, float* finals, lsr_result* results);
 int gicp_get_covariances(lsr_handle_s* h, int which, double* cov);
 int gicp_linearize(lsr_handle_s* h, const float* guess, const float* trans, int use_seeds, const GicpLinearizeOut& out);
+int gicp_bfgs_trace(lsr_handle_s* h, const float* guess, const float* trans, int capacity, const GicpBfgsTraceOut& out);
 // lsr_prepare_target: neighbour grid + k-NN covariances of the current target on h's stream, complete on return (no source needed)
 int gicp_prepare_target(lsr_handle_s* h);
 // nothing of the current target is left for an align with h's k_correspondences / gicp_epsilon to build

@@ -67,6 +67,7 @@ class FrontendParams:   # scanmatcher_component.cpp:36-60 (declare_parameter def
     scan_max_range: float = 100.0
     num_targeted_cloud: int = 10
     registration_method: str = "NDT"   # :98-125 — "NDT" or "GICP"
+    gicp_solver: str = "gauss_newton"  # GICP mode: the inner optimiser of `reg` — "gauss_newton", or "bfgs" (the reference's own schedule)
     use_imu: bool = False              # :78 — de-skew the raw scan with the IMU queue before the range filter (:204-208)
     scan_period: float = 0.1           # :80 — lidar_undistortion_.setScanPeriod
 
@@ -95,6 +96,13 @@ class FrontendReplay:
         self.p = params or FrontendParams()
         if self.p.registration_method not in ("NDT", "GICP"):
             raise ValueError("registration_method must be \"NDT\" or \"GICP\" (scanmatcher_component.cpp:121-124)")
+        if self.p.gicp_solver not in ("gauss_newton", "bfgs"):
+            raise ValueError("gicp_solver must be \"gauss_newton\" or \"bfgs\"")
+        if self.p.registration_method == "GICP":   # the object that aligns follows the parameter (a builder never aligns)
+            if hasattr(reg, "setOptimizer"):
+                reg.setOptimizer(self.p.gicp_solver)
+            elif self.p.gicp_solver != "gauss_newton":
+                raise ValueError("gicp_solver = \"bfgs\" needs a registration object with setOptimizer")
         self.to_device = to_device or (lambda a: a)
         # `mapper` (optional): a second registration object whose input-source slot serves as the map side's filter — with it and a
         # device-resident payload the new keyframe (range filter + VoxelGrid(vg_size_for_map)) is produced and kept in HBM

@@ -38,6 +38,7 @@ class LoopClosureParams:
     search_submap_num: int = 3                      # :37
     voxel_leaf_size: float = 0.2                    # :23
     top_k: int = 1                                  # 1 = the reference (nearest candidate only)
+    gicp_solver: str = "gauss_newton"               # a GICP `registration`: its inner optimiser — "gauss_newton" or "bfgs" (the reference's)
 
 
 @dataclass
@@ -56,6 +57,10 @@ class LoopEdge:
 def search_loop(registration: Registration, submaps: Sequence[SubMap], params: LoopClosureParams = LoopClosureParams()) -> List[LoopEdge]:
     """All candidate evaluations, nearest candidate first (empty list = no candidate passed the distance gates)."""
     lib = _capi.load()
+    if params.gicp_solver not in ("gauss_newton", "bfgs"):
+        raise ValueError("gicp_solver must be \"gauss_newton\" or \"bfgs\"")
+    if hasattr(registration, "setOptimizer"):   # a GICP object: every candidate's align follows it (the key travels with the object)
+        registration.setOptimizer(params.gicp_solver)
     n = len(submaps)
     if n == 0:
         return []

@@ -731,6 +731,41 @@ class GeneralizedIterativeClosestPoint(Registration):
         r["m"] = int(m.value)
         return r
 
+    _OPTIMIZERS = {"gauss_newton": capi.GICP_GAUSS_NEWTON, "bfgs": capi.GICP_BFGS}
+
+    def setOptimizer(self, name: str):
+        """The inner optimiser of align(): "gauss_newton" (default) or "bfgs", the reference's own schedule (LSR_GICP_SOLVER)."""
+        if name not in self._OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {sorted(self._OPTIMIZERS)}, not {name!r}")
+        self._seti(capi.GICP_SOLVER, self._OPTIMIZERS[name], "setOptimizer")
+
+    def getOptimizer(self) -> str:
+        v = self._geti(capi.GICP_SOLVER)
+        return next(k for k, c in self._OPTIMIZERS.items() if c == v)
+
+    BFGS_REASONS = {0: "running", 1: "no_progress", 2: "gradient_tolerance", 3: "max_inner", 4: "non_finite"}
+
+    def bfgs_trace(self, guess=None, trans=None, capacity: int = 4096) -> dict:
+        """Inspection (lsr_gicp_bfgs_trace): ONE outer iteration of align(guess) under the BFGS optimiser — the correspondence pass at
+        transformation_ = `trans` (4x4, None = identity) and the whole inner loop — run by align's own launches.
+        Returns x (e,6), f (e,), g (e,6), inner (e,) per evaluation (the first `capacity`), n_evals, n_inner, reason (code) and
+        reason_name, x_final (6,), m."""
+        fp, dp, ip = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        g = _mat_to_col16(guess) if guess is not None else None
+        t = _mat_to_col16(trans) if trans is not None else None
+        cap = max(int(capacity), 0)
+        x, f, gr = np.zeros((max(cap, 1), 6)), np.zeros(max(cap, 1)), np.zeros((max(cap, 1), 6))
+        inner = np.zeros(max(cap, 1), np.int32)
+        xf = np.zeros(6)
+        ne, ni, why, m = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        capi.check(self._lib.lsr_gicp_bfgs_trace(
+            self._h, g.ctypes.data_as(fp) if g is not None else None, t.ctypes.data_as(fp) if t is not None else None, cap,
+            x.ctypes.data_as(dp), f.ctypes.data_as(dp), gr.ctypes.data_as(dp), inner.ctypes.data_as(ip), C.byref(ne), C.byref(ni),
+            C.byref(why), xf.ctypes.data_as(dp), C.byref(m)), "bfgs_trace")
+        e = min(int(ne.value), cap)
+        return dict(x=x[:e], f=f[:e], g=gr[:e], inner=inner[:e], n_evals=int(ne.value), n_inner=int(ni.value),
+                    reason=int(why.value), reason_name=self.BFGS_REASONS.get(int(why.value), "?"), x_final=xf, m=int(m.value))
+
 
 def set_input_target_batch(regs: Sequence[Registration], clouds):
     """setInputTarget of every candidate of a set with the builds overlapped on the device (lsr_set_input_target_batch;
