@@ -1,5 +1,5 @@
 """Per-launch durations of the NDT chain kernels from a rocprofv3 kernel-trace CSV (last align of tools/chain_probe.py).
-A set of six or more members runs as TWO launch chains on two streams (capi.hip: run_ndt_feeder): the launches are listed per
+A set of six or more members runs as TWO launch chains on two streams (ndt_align.hip: run_ndt_feeder): the launches are listed per
 stream; `gap` = end of a launch -> start of the next launch on the SAME stream."""
 import csv, sys, glob, collections
 path = sys.argv[1]
