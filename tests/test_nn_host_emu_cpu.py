@@ -1,7 +1,9 @@
 """CPU tests of the DEVICE nearest-neighbour search code (lidarslam_ros2_amd/csrc/nn_device.hpp) compiled for the host
 (tools/nn_host_emu/harness.cpp): the per-thread walk with its row pruning and x clipping against brute force — indices and
 fp32 distances bit for bit, ties by lowest index —, and the slot enumeration of the wave-cooperative search: the segments of
-a shell cover the shell's cells exactly once, and pruning / clipping never drop a point that could still matter."""
+a shell cover the shell's cells exactly once, and pruning / clipping never drop a point that could still matter.  The walk
+capped at two fine shells (nn1_kernel for more than 262 144 queries) never reports a wrong neighbour as proven, and reports as
+NOT proven every query the GPU tests count on to reach the work list."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +11,8 @@ import sys
 
 import numpy as np
 import pytest
+
+from nn_numpy import NN_MAX_FINE_RINGS, brute_nn, brute_nn1, build_grid, cells_outside, clouds, face_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,31 +29,6 @@ def emu(tmp_path_factory):
     return C.CDLL(str(d / "libnnh.so"))
 
 
-def build_grid(pts, cell):
-    """The two-level grid of nn.hip, built with numpy (points ordered by (coarse cell, fine cell), stable)."""
-    inv = np.float32(1.0) / np.float32(cell)
-    f = np.floor(pts * inv).astype(np.int64)
-    f0, f1 = f.min(0), f.max(0)
-    org = np.where(f0 >= 0, f0 & ~7, -(((-f0) + 7) & ~7))
-    cdim = ((f1 - org) >> 3) + 1
-    rel = f - org
-    cc = rel >> 3
-    clin = cc[:, 0] + cdim[0] * (cc[:, 1] + cdim[1] * cc[:, 2])
-    fine = (rel[:, 0] & 7) | ((rel[:, 1] & 7) << 3) | ((rel[:, 2] & 7) << 6)
-    order = np.argsort(clin * 512 + fine, kind="stable").astype(np.int32)
-    ublk = np.unique(clin)
-    coarse_block = -np.ones(int(np.prod(cdim)), np.int32)
-    coarse_block[ublk] = np.arange(len(ublk), dtype=np.int32)
-    blk_of = coarse_block[clin[order]]
-    fkey = blk_of.astype(np.int64) * 513 + fine[order]
-    fine_start = np.searchsorted(fkey, np.arange(len(ublk) * 513), side="left").astype(np.int32)
-    block_off = np.searchsorted(blk_of, np.arange(len(ublk) + 1), side="left").astype(np.int32)
-    s = pts[order]
-    return dict(cell=np.float32(cell), org=org.astype(np.int32), cdim=cdim.astype(np.int32), coarse_block=coarse_block, block_off=block_off,
-                fine_start=fine_start, sx=np.ascontiguousarray(s[:, 0]), sy=np.ascontiguousarray(s[:, 1]), sz=np.ascontiguousarray(s[:, 2]),
-                order=order, rel=rel, pts=pts)
-
-
 def P(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -57,27 +36,6 @@ def P(a, t):
 def grid_args(g):
     return (C.c_float(float(g["cell"])), P(g["org"], C.c_int), P(g["cdim"], C.c_int), P(g["coarse_block"], C.c_int), P(g["block_off"], C.c_int),
             P(g["fine_start"], C.c_int), P(g["sx"], C.c_float), P(g["sy"], C.c_float), P(g["sz"], C.c_float), P(g["order"], C.c_int), len(g["order"]))
-
-
-def brute_nn1(pts, q):
-    """(distance, index) minimum with the device's fp32 arithmetic: ((dx*dx + dy*dy) + dz*dz), no contraction."""
-    d = (pts - q[None, :]).astype(np.float32)
-    d2 = ((d[:, 0] * d[:, 0]).astype(np.float32) + (d[:, 1] * d[:, 1]).astype(np.float32)).astype(np.float32)
-    d2 = (d2 + (d[:, 2] * d[:, 2]).astype(np.float32)).astype(np.float32)
-    j = int(np.lexsort((np.arange(len(pts)), d2))[0])
-    return j, d2[j]
-
-
-def clouds():
-    from lidarslam_ros2_amd import synth
-
-    rng = np.random.default_rng(3)
-    case = synth.small_case(n_source=1500, n_keyframes=2)
-    dup = rng.uniform(-4, 4, (300, 3)).astype(np.float32)
-    dup = np.vstack([dup, dup[:150]])            # exact duplicates: ties broken by the lowest index
-    lattice = (np.stack(np.meshgrid(*[np.arange(-6, 6)] * 3, indexing="ij"), -1).reshape(-1, 3) * 0.5).astype(np.float32)   # points ON cell faces
-    return [("uniform", rng.uniform(-12, 12, (4000, 3)).astype(np.float32)), ("scan", case.target[:6000].astype(np.float32)), ("duplicates", dup),
-            ("lattice", lattice)]
 
 
 @pytest.mark.parametrize("cell", [0.5, 0.3, 1.0])
@@ -165,3 +123,63 @@ def test_ball_cell_range_holds_every_point_of_the_ball(emu, cell):
             assert np.all((rel[inside] >= lo[None, :]) & (rel[inside] <= hi[None, :])), (name, cell, q, lo, hi)
             assert np.all(hi - lo <= 2)
             assert (rel[j] >= lo).all() and (rel[j] <= hi).all()   # in particular the true nearest neighbour
+
+
+def capped_queries(pts, cell, rng):
+    """The query mix of this file (near, anywhere, exact hits) and a point per face of the box one and six cells outside it."""
+    return np.vstack([pts[rng.integers(0, len(pts), 150)] + rng.normal(0, 0.2, (150, 3)).astype(np.float32),
+                      rng.uniform(-15, 15, (50, 3)).astype(np.float32), pts[:30], face_points(pts, cell)]).astype(np.float32)
+
+
+def run_capped(emu, g, q, fine_rings, max_d2, ring_cap=2):
+    qx, qy, qz = [np.ascontiguousarray(q[:, k]) for k in range(3)]
+    idx, d2, flag = np.zeros(len(q), np.int32), np.zeros(len(q), np.float32), np.zeros(len(q), np.int32)
+    n_not = emu.run_nn1_capped(*grid_args(g), P(qx, C.c_float), P(qy, C.c_float), P(qz, C.c_float), len(q), fine_rings, C.c_float(max_d2),
+                               ring_cap, P(idx, C.c_int), P(d2, C.c_float), P(flag, C.c_int))
+    assert n_not == flag.sum()
+    return idx, d2, flag.astype(bool)
+
+
+@pytest.mark.parametrize("cell", [0.5, 0.37, 0.4625])
+def test_capped_walk_never_lies(emu, cell):
+    """ring_cap = 2: whatever the walk reports as proven is brute force's (index, d2) — a wrong `true` would be a wrong neighbour
+    that nothing downstream notices.  With a gate, the answer is exact wherever the true d2 is inside the gate; outside it the
+    walk may stop early, and then it must not have kept a point inside the gate."""
+    rng = np.random.default_rng(23)
+    n_proven = n_deferred = 0
+    for name, pts in clouds():
+        g = build_grid(pts, cell)
+        q = capped_queries(pts, cell, rng)
+        ridx, rd2 = brute_nn(pts, q)
+        for fine_rings in (0, 1):
+            idx, d2, deferred = run_capped(emu, g, q, fine_rings, np.inf)
+            ok = ~deferred
+            assert np.array_equal(idx[ok], ridx[ok]) and np.array_equal(d2[ok], rd2[ok]), (name, cell, fine_rings)
+            n_proven += ok.sum(); n_deferred += deferred.sum()
+            gate = np.float32(0.25)
+            idx, d2, deferred = run_capped(emu, g, q, fine_rings, gate)
+            ok = ~deferred & (rd2 <= gate)
+            assert np.array_equal(idx[ok], ridx[ok]) and np.array_equal(d2[ok], rd2[ok]), (name, cell, fine_rings, "gate")
+            out = ~deferred & (rd2 > gate)
+            assert not np.any((idx[out] >= 0) & (d2[out] <= gate)), (name, cell, fine_rings, "a pair inside the gate was invented")
+    assert n_proven > 1000 and n_deferred > 200      # both outcomes occur
+
+
+@pytest.mark.parametrize("cell", [0.5, 0.37, 0.4625])
+def test_capped_walk_defers_what_it_cannot_prove(emu, cell):
+    """The predicate the large-query GPU tests count with: a query whose nearest point is more than 3 cells away (after shell 2
+    the bound is at most 3 cells), or that lies more than NN_MAX_FINE_RINGS cells outside the grid box, is NOT proven."""
+    rng = np.random.default_rng(29)
+    seen_far = seen_out = 0
+    for name, pts in clouds():
+        g = build_grid(pts, cell)
+        q = capped_queries(pts, cell, rng)
+        _, rd2 = brute_nn(pts, q)
+        far = np.sqrt(rd2.astype(np.float64)) > 3.0 * cell
+        outside = cells_outside(q, cell, g["org"], g["cdim"]) > NN_MAX_FINE_RINGS
+        for fine_rings in (0, 1):
+            _, _, deferred = run_capped(emu, g, q, fine_rings, np.inf)
+            assert deferred[far].all(), (name, cell, fine_rings, "a query farther than three cells was reported proven")
+            assert deferred[outside].all(), (name, cell, fine_rings, "a query outside the fine range was reported proven")
+        seen_far += far.sum(); seen_out += outside.sum()
+    assert seen_far > 100 and seen_out > 50

@@ -73,6 +73,26 @@ extern "C" long run_nn1(float cell, const int* org, const int* cdim, const int* 
   return 0;
 }
 
+// the same walk with a ring cap, as nn1_kernel runs it for large query sets (run_nn1 keeps its argument list: callers built against
+// it pass no cap).  ring_cap < 0: the walk always completes; ring_cap >= 0: only fine shells 0..ring_cap, and not_proven[i] = 1 for
+// a query the walk hands on (nn1_kernel puts it on the work list and writes nothing; out_idx / out_d2 then hold what the capped
+// walk had seen, for inspection only).  Returns the number of queries not proven.
+extern "C" long run_nn1_capped(float cell, const int* org, const int* cdim, const int* coarse_block, const int* block_off, const int* fine_start,
+             const float* sx, const float* sy, const float* sz, const int* order, int n_pts, const float* qx, const float* qy, const float* qz, int nq,
+             int fine_rings, float max_d2, int ring_cap, int* out_idx, float* out_d2, int* not_proven) {
+  NNGridView G = make_grid(cell, org, cdim, coarse_block, block_off, fine_start, sx, sy, sz, order, n_pts);
+  long n_not = 0;
+  for (int i = 0; i < nq; i++) {
+    Best1 c; c.init();
+    const bool proven = nn_query(G, qx[i], qy[i], qz[i], fine_rings, max_d2, c, -1, ring_cap);
+    out_idx[i] = c.idx; out_d2[i] = c.d2;
+    if (not_proven) not_proven[i] = proven ? 0 : 1;
+    n_not += proven ? 0 : 1;
+  }
+  free((void*)G.p);
+  return n_not;
+}
+
 // the segments fine_segment() hands out for shell r of one query: out[2 * slot] = beg, out[2 * slot + 1] = len for the
 // 4 (2r+1)^2 slots.  full != 0: with pruning / clipping against `worst`.
 extern "C" long run_shell_segments(float cell, const int* org, const int* cdim, const int* coarse_block, const int* block_off, const int* fine_start,
