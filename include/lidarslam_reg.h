@@ -322,6 +322,53 @@ int lsr_deskew_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc
  * nothing when that call moved nothing because the ring was too short. */
 int lsr_deskew_trace(lsr_handle h, float* rel_time, int32_t* slot, uint8_t* skipped);
 
+/* ---- raw scan into the robot frame; the use_odom guess (scanmatcher_component.cpp:188-199, 333-348) ------------
+ * The cloud callback moves every scan from the sensor frame (msg->header.frame_id) into robot_frame_id_ before anything else reads
+ * it: the de-skew, the range filter and the map side are all defined on robot-frame coordinates.  The arithmetic is this library's
+ * definition (tf2's source is not part of the reference checkout: restated, unpinned):
+ *  - the matrix: translation and quaternion (x y z w, NOT normalised), all double, become a double 4x4 in the expression order every
+ *    pose message of the library goes through (Translation * Quaterniond, Eigen's toRotationMatrix); its top three rows are cast to
+ *    fp32 element by element;
+ *  - the point: x' = ((m00*x + m01*y) + m02*z) + m03, likewise y' and z', every product and sum rounded to fp32, no FMA — the bits
+ *    lsr_assemble_map gives the same point and pose;
+ *  - a record with a non-finite coordinate comes out with non-finite coordinates, as that arithmetic gives them; every byte of a
+ *    record that is not x, y or z is copied. */
+typedef struct lsr_sensor_transform {
+  double translation[3];        /* geometry_msgs/Transform.translation x y z */
+  double rotation_xyzw[4];      /* geometry_msgs/Transform.rotation x y z w */
+} lsr_sensor_transform;
+/* tfbuffer_.lookupTransform(robot_frame_id_, msg->header.frame_id, time_point)   scanmatcher_component.cpp:193-194: the result as the
+ * kernels use it — out12 = rows 0-2 of the fp32 matrix, row-major.  Needs no device and no handle. */
+int lsr_sensor_transform_matrix(const lsr_sensor_transform* tf, float* out12);
+/* tf2::doTransform(*msg, transformed_msg, transform)   scanmatcher_component.cpp:195
+ * data: n_points records of layout->point_step bytes; out_data: the same records with x / y / z moved.  on_device != 0: both are HIP
+ * device pointers (ordering rules as for every device input above), equal (in place) or disjoint (ranges that overlap otherwise:
+ * LSR_ERR_INVALID_ARGUMENT); the call returns when the records are complete, for a reader on any stream, and performs no
+ * device-to-host copy and no stream synchronisation.  on_device == 0: both are host pointers, equal or disjoint (upload, kernel,
+ * download).  n_points == 0: LSR_OK, nothing is touched.  This is the form in front of lsr_deskew_pc2 on the use_imu path (:204-208 read
+ * the transformed cloud) and the one a host-side map path uses; without IMU the scan side needs no pass of its own:
+ * lsr_set_input_source_pc2_tf. */
+int lsr_transform_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, const lsr_sensor_transform* tf,
+                      int on_device, void* out_data);
+/* lsr_set_input_source_pc2 from a payload in the SENSOR frame: doTransform (:195) -> fromROSMsg (:201-202) -> range filter (:210-218) ->
+ * VoxelGrid (:324-328) -> setInputSource (:329).  The transform is applied as the records are read, in the one launch that also filters
+ * the range and takes the bounding box — both see robot-frame points; the source is, bit for bit, what lsr_transform_pc2 followed by
+ * lsr_set_input_source_pc2 leaves.  tf == NULL: exactly lsr_set_input_source_pc2. */
+int lsr_set_input_source_pc2_tf(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout,
+                                const lsr_sensor_transform* tf, double scan_min_range, double scan_max_range, float vg_size_for_input,
+                                int on_device, size_t* n_out);
+/* receiveCloud's use_odom guess   scanmatcher_component.cpp:333-348
+ * sim_trans16: the previous pose (getTransformation(corrent_pose_stamped_.pose), :331); odom16: odom_frame_id_ -> robot_frame_id_ at the
+ * scan's stamp as a matrix (:342-343); previous_odom16: the same of the scan before, the identity before the first (previous_odom_mat_);
+ * all column-major fp32.  previous_odom16 the identity — every entry == its entry of the identity, as Eigen's `previous_odom_mat_ !=
+ * Identity()` (:344) compares: the identity's bits, or -0 for a 0 —: guess16 = sim_trans16, bit for bit (the first scan and, a quirk
+ * that is kept, an odometry that truly reads identity).  Otherwise guess16 =
+ * sim_trans * previous_odom^-1 * odom (:345), computed in double from the fp32 inputs (general 4x4 inverse) and rounded once to fp32.
+ * DEVIATION: the reference multiplies in float and inverts with Eigen's Matrix4f::inverse(), a float cofactor inverse whose bits
+ * cannot be restated without Eigen's source; this entry is within one rounding of the exact product instead.  The caller keeps
+ * previous_odom (:347).  The only implementation: the C++ classes and the Python binding call it.  Needs no device and no handle. */
+int lsr_odom_guess(const float* sim_trans16, const float* previous_odom16, const float* odom16, float* guess16);
+
 /* Let `h` register against the target already resident in `owner` (N keyframes vs ONE submap):
  * no copy, the voxel grid / target structures are reference counted. */
 int lsr_share_target(lsr_handle h, lsr_handle owner);

@@ -97,6 +97,36 @@ class Gfx950Registration : public pcl::Registration<PointSource, PointTarget> {
     report(st);
     return st == LSR_OK;
   }
+  // ---- the head of the cloud callback (:188-199) and the use_odom guess (:333-348) ----
+  // lookupTransform(robot_frame_id_, msg->header.frame_id) (:193-194), kept on the object: setInputSourcePointCloud2 below moves the
+  // payload by it as it reads the records
+  void setSensorTransform(const lsr_sensor_transform& tf) { sensor_tf_ = tf; has_sensor_tf_ = true; }
+  void clearSensorTransform() { has_sensor_tf_ = false; }
+  // tf2::doTransform (:195) on the raw PointCloud2 payload, records in, records out (host or device pointers, equal or disjoint): the
+  // step in front of deskewPointCloud2 (use_imu) and of a host-side map path
+  bool transformPointCloud2(const void* data, std::size_t n_points, const lsr_pc2_layout& layout, const lsr_sensor_transform& tf,
+                            void* out_data, bool on_device = false) {
+    const int st = lsr_transform_pc2(h_, data, n_points, &layout, &tf, on_device ? 1 : 0, out_data);
+    report(st);
+    return st == LSR_OK;
+  }
+  // doTransform (:195, when a sensor transform is set) -> fromROSMsg (:201-202) -> range filter (:210-218) -> VoxelGrid (:324-328) ->
+  // setInputSource (:329) from the raw payload; input_ is not touched (the filtered cloud stays in HBM: lsr_get_source_pc2 reads it)
+  bool setInputSourcePointCloud2(const void* data, std::size_t n_points, const lsr_pc2_layout& layout, double scan_min_range,
+                                 double scan_max_range, float vg_size_for_input, bool on_device = false, std::size_t* n_kept = nullptr) {
+    epoch_++;
+    const int st = lsr_set_input_source_pc2_tf(h_, data, n_points, &layout, has_sensor_tf_ ? &sensor_tf_ : nullptr, scan_min_range,
+                                               scan_max_range, vg_size_for_input, on_device ? 1 : 0, n_kept);
+    report(st);
+    return st == LSR_OK;
+  }
+  // sim_trans * previous_odom_mat_.inverse() * odom_mat (:345; previous_odom exactly the identity: sim_trans, :344).  The caller
+  // keeps previous_odom_mat_ = odom_mat (:347)
+  static Eigen::Matrix4f odomGuess(const Eigen::Matrix4f& sim_trans, const Eigen::Matrix4f& previous_odom, const Eigen::Matrix4f& odom) {
+    Eigen::Matrix4f guess = sim_trans;
+    lsr_odom_guess(sim_trans.data(), previous_odom.data(), odom.data(), guess.data());
+    return guess;
+  }
   // align(output, ...) fills `output` with the transformed source like PCL does (12 bytes per point cross PCIe).  Both
   // reference callers discard it (scanmatcher_component.cpp:350-353, graph_based_slam_component.cpp:229-230): they switch
   // it off and `output` keeps the plain copy of the source pcl::Registration::align made.
@@ -172,6 +202,8 @@ class Gfx950Registration : public pcl::Registration<PointSource, PointTarget> {
   }
 
   lsr_handle h_ = nullptr;
+  lsr_sensor_transform sensor_tf_ = {{0, 0, 0}, {0, 0, 0, 1}};   // setSensorTransform
+  bool has_sensor_tf_ = false;
   bool materialize_output_ = true;
   unsigned long epoch_ = 1, nn_epoch_ = 0;       // bumped by setInputTarget / setInputSource / align; epoch of the cached search
   std::vector<int32_t> nn_idx_;

@@ -102,6 +102,36 @@ class Registration {
     check(st, "deskewPointCloud2");
     return st == LSR_OK;
   }
+  // ---- raw scan into the robot frame; the use_odom guess ----
+  // tfbuffer_.lookupTransform(robot_frame_id_, msg->header.frame_id, ..)   scanmatcher_component.cpp:193-194
+  // kept on the object; setInputSourcePointCloud2 below moves the payload by it as it reads the records
+  void setSensorTransform(const lsr_sensor_transform& tf) { sensor_tf_ = tf; has_sensor_tf_ = true; }
+  void clearSensorTransform() { has_sensor_tf_ = false; }
+  // tf2::doTransform(*msg, transformed_msg, transform)                    scanmatcher_component.cpp:195
+  // raw PointCloud2 payload in, robot-frame payload out (host or device pointers, equal or disjoint): the step in front of
+  // deskewPointCloud2 (use_imu) and of a host-side map path
+  bool transformPointCloud2(const void* data, size_t n_points, const lsr_pc2_layout& layout, const lsr_sensor_transform& tf, void* out_data,
+                            bool on_device = false) {
+    const int st = lsr_transform_pc2(h_, data, n_points, &layout, &tf, on_device ? 1 : 0, out_data);
+    check(st, "transformPointCloud2");
+    return st == LSR_OK;
+  }
+  // doTransform (:195, when a sensor transform is set) -> fromROSMsg (:201-202) -> range filter (:210-218) -> VoxelGrid (:324-328) ->
+  // setInputSource (:329) from the raw payload, one launch for everything in front of the filter
+  bool setInputSourcePointCloud2(const void* data, size_t n_points, const lsr_pc2_layout& layout, double scan_min_range, double scan_max_range,
+                                 float vg_size_for_input, bool on_device = false, size_t* n_kept = nullptr) {
+    const int st = lsr_set_input_source_pc2_tf(h_, data, n_points, &layout, has_sensor_tf_ ? &sensor_tf_ : nullptr, scan_min_range,
+                                               scan_max_range, vg_size_for_input, on_device ? 1 : 0, n_kept);
+    check(st, "setInputSourcePointCloud2");
+    return st == LSR_OK;
+  }
+  // sim_trans * previous_odom_mat_.inverse() * odom_mat                   scanmatcher_component.cpp:333-348
+  // (previous_odom exactly the identity: sim_trans; the caller keeps previous_odom = odom, :347)
+  static Matrix4f odomGuess(const Matrix4f& sim_trans, const Matrix4f& previous_odom, const Matrix4f& odom) {
+    Matrix4f guess = sim_trans;
+    lsr_odom_guess(sim_trans.data(), previous_odom.data(), odom.data(), guess.data());
+    return guess;
+  }
   const lsr_result& lastResult() const { return last_; }
   lsr_handle handle() const { return h_; }
 
@@ -227,6 +257,8 @@ class Registration {
   PointCloudTargetConstPtr target_;
   Matrix4f final_;
   lsr_result last_;
+  lsr_sensor_transform sensor_tf_ = {{0, 0, 0}, {0, 0, 0, 1}};   // setSensorTransform
+  bool has_sensor_tf_ = false;
 };
 
 // pclomp::NormalDistributionsTransform<PointSource,PointTarget>   scanmatcher_component.cpp:105-113

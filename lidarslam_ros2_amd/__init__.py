@@ -5,11 +5,11 @@ getFitnessScore) is implemented here — hand-written HIP kernels for gfx950 beh
 include/lidarslam_reg.h.  See DESIGN.md.
 """
 from .registration import (DIRECT1, DIRECT7, DIRECT26, KDTREE, GeneralizedIterativeClosestPoint,
-                           NormalDistributionsTransform, Registration, align_batch)
+                           NormalDistributionsTransform, Registration, align_batch, odomGuess, sensorTransformMatrix)
 from .loop_closure import LoopClosureParams, LoopEdge, SubMap, search_loop
 from .map_array import MapArray
 from . import pose_graph
 
 __all__ = ["Registration", "NormalDistributionsTransform", "GeneralizedIterativeClosestPoint", "align_batch",
-           "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray", "pose_graph",
+           "odomGuess", "sensorTransformMatrix", "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray", "pose_graph",
            "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]

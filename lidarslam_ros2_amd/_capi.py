@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "lsr_imu_reset", "lsr_imu_push", "lsr_imu_receive", "lsr_imu_info", "lsr_deskew_pc2", "lsr_deskew_trace",
     "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long",
     "lsr_format_pcd_ascii", "lsr_save_pcd_ascii", "lsr_save_map_pcd_ascii", "lsr_gicp_bfgs_trace",
+    "lsr_sensor_transform_matrix", "lsr_transform_pc2", "lsr_set_input_source_pc2_tf", "lsr_odom_guess",
 ]
 
 
@@ -98,6 +99,10 @@ class Pc2Layout(C.Structure):
 
 class DeskewInfo(C.Structure):
     _fields_ = [("n_skipped", C.c_int32), ("start_missing", C.c_int32), ("half_index", C.c_int32), ("cursor", C.c_int32)]
+
+
+class SensorTransform(C.Structure):
+    _fields_ = [("translation", C.c_double * 3), ("rotation_xyzw", C.c_double * 4)]
 
 
 class ShardRecord(C.Structure):
@@ -206,6 +211,11 @@ def load() -> C.CDLL:
     L.lsr_imu_info.argtypes = [vp, i32p]
     L.lsr_deskew_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_int, vp, C.POINTER(DeskewInfo)]
     L.lsr_deskew_trace.argtypes = [vp, fp, i32p, C.POINTER(C.c_uint8)]
+    L.lsr_sensor_transform_matrix.argtypes = [C.POINTER(SensorTransform), fp]
+    L.lsr_transform_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.POINTER(SensorTransform), C.c_int, vp]
+    L.lsr_set_input_source_pc2_tf.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.POINTER(SensorTransform), C.c_double, C.c_double,
+                                              C.c_float, C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_odom_guess.argtypes = [fp, fp, fp, fp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int or name not in ("lsr_version", "lsr_status_string", "lsr_last_error"):

@@ -1,8 +1,9 @@
 // The clouds on their way into and out of the registration object: PointXYZI records or a PointCloud2
 // payload -> SoA planes (+ the frontend's range filter and the bounding-box records in one pass), pcl::VoxelGrid (leaf keys with the
 // grid dimensions worked out on the device, stable LSD sort, run heads, float centroids in ascending point index), SoA planes ->
-// records / PointCloud2 payload, pcl::transformPointCloud into strided records.  Reference call sites:
-// scanmatcher_component.cpp:201-218,279-284,324-329,443-447.  (Split out of ndt.hip in round 6: same code.)
+// records / PointCloud2 payload, pcl::transformPointCloud into strided records, tf2::doTransform of a raw payload into the robot frame
+// (fused into the ingest pass, or records -> records).  Reference call sites:
+// scanmatcher_component.cpp:195,201-218,279-284,324-329,443-447.  (Split out of ndt.hip in round 6: same code.)
 #include "ndt.hpp"
 
 #include <cmath>
@@ -12,6 +13,7 @@
 #include "build_kernels.hpp"
 #include "grid_device.hpp"
 #include "sort.hpp"
+#include "xform_ref.hpp"
 
 namespace lsr {
 
@@ -343,11 +345,15 @@ namespace {
 //   follows drops it exactly like non-finite input.
 //   bounding box: the workgroup records go to the host mailbox (cloud_bbox_end folds them as it folds bbox_kernel's) and, the same
 //   words, to device memory for voxel_grid_filter's device-side dimensions.
+//   TF (lsr_set_input_source_pc2_tf): the scan arrives in the sensor frame and is moved into the robot frame as it is read
+//   (tf2::doTransform, scanmatcher_component.cpp:195) — before the range test, the NaN marking and the box, which are all defined on
+//   robot-frame coordinates.  The twelve floats travel in the kernel arguments; the untransformed instantiation never reads them.
+template <bool TF>
 __global__ __launch_bounds__(256) void pc2_ingest_kernel(const unsigned char* __restrict__ data, int step, int ox, int oy, int oz, int oi,
                                                          int n, float* __restrict__ x, float* __restrict__ y, float* __restrict__ z,
                                                          float* __restrict__ w, int do_range, double rmin, double rmax,
                                                          unsigned long long* __restrict__ parts_dev, BuildMailbox* __restrict__ mb,
-                                                         unsigned int token) {
+                                                         unsigned int token, const SensorTf12 tf) {
   float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
   unsigned int cnt = 0;
   const int step_pts = gridDim.x * blockDim.x;
@@ -364,6 +370,15 @@ __global__ __launch_bounds__(256) void pc2_ingest_kernel(const unsigned char* __
         p[u][3] = (w && oi >= 0) ? *reinterpret_cast<const float*>(rec + oi) : 0.f;
       } else {
         p[u][0] = p[u][1] = p[u][2] = NAN; p[u][3] = 0.f;
+      }
+    }
+    if (TF) {
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const float sx = p[u][0], sy = p[u][1], sz = p[u][2];
+        p[u][0] = xform_ref(tf.m[0], tf.m[1], tf.m[2], tf.m[3], sx, sy, sz);
+        p[u][1] = xform_ref(tf.m[4], tf.m[5], tf.m[6], tf.m[7], sx, sy, sz);
+        p[u][2] = xform_ref(tf.m[8], tf.m[9], tf.m[10], tf.m[11], sx, sy, sz);
       }
     }
 #pragma unroll
@@ -410,8 +425,64 @@ __global__ __launch_bounds__(256) void pc2_ingest_kernel(const unsigned char* __
 }
 }  // namespace
 
+namespace {
+// tf2::doTransform(*msg, transformed_msg, transform) on a payload (scanmatcher_component.cpp:195), one record per thread: x / y / z moved by
+// xform_ref, every other byte of the record copied.  in == out (in place) or disjoint.  The records of a workgroup are contiguous: for a
+// disjoint output they are copied as words by the whole workgroup first, the coordinates are stored over the copy.  A thread reads no
+// record of `in` but its own, and in place nothing else is written.
+__global__ __launch_bounds__(256) void pc2_transform_kernel(const unsigned char* in, unsigned char* out, int step, int ox, int oy, int oz,
+                                                            int n, const SensorTf12 tf) {
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * 256 + tid;
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  if (i < n) {
+    const unsigned char* rec = in + (size_t)i * step;
+    sx = *reinterpret_cast<const float*>(rec + ox);
+    sy = *reinterpret_cast<const float*>(rec + oy);
+    sz = *reinterpret_cast<const float*>(rec + oz);
+  }
+  if (out != in) {   // uniform over the launch
+    const size_t first = (size_t)blockIdx.x * 256;
+    const size_t count = min((size_t)256, (size_t)n - first);
+    const unsigned int* src = reinterpret_cast<const unsigned int*>(in + first * step);
+    unsigned int* dst = reinterpret_cast<unsigned int*>(out + first * step);
+    const size_t words = count * (size_t)(step / 4);
+    for (size_t k = tid; k < words; k += 256) dst[k] = src[k];
+    __syncthreads();   // the copy precedes the coordinate stores below (other threads wrote this thread's record)
+  }
+  if (i < n) {
+    unsigned char* o = out + (size_t)i * step;
+    *reinterpret_cast<float*>(o + ox) = xform_ref(tf.m[0], tf.m[1], tf.m[2], tf.m[3], sx, sy, sz);
+    *reinterpret_cast<float*>(o + oy) = xform_ref(tf.m[4], tf.m[5], tf.m[6], tf.m[7], sx, sy, sz);
+    *reinterpret_cast<float*>(o + oz) = xform_ref(tf.m[8], tf.m[9], tf.m[10], tf.m[11], sx, sy, sz);
+  }
+}
+
+// the completion word of pc2_transform: one system-scope store behind the transform launch, which has ended when this one starts
+__global__ void pc2_transform_publish_kernel(BuildMailbox* __restrict__ mb, unsigned int token) {
+  __hip_atomic_store(&mb->tf_token, token, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+}  // namespace
+
+int pc2_transform(const void* d_in, void* d_out, int step, int ox, int oy, int oz, size_t n, const SensorTf12& tf, BuildScratch& sc,
+                  hipStream_t stream, bool wait) {
+  if (n == 0) return LSR_OK;
+  int st;
+  if (wait && (st = sc.ensure_mailbox())) return st;
+  const unsigned int nb = (unsigned int)((n + 255) / 256);
+  hipLaunchKernelGGL(pc2_transform_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned char*)d_in, (unsigned char*)d_out, step, ox, oy, oz,
+                     (int)n, tf);
+  LSR_HIP(hipGetLastError());
+  if (!wait) return LSR_OK;
+  unsigned int token = ++sc.token;
+  if (token == 0) token = ++sc.token;
+  hipLaunchKernelGGL(pc2_transform_publish_kernel, dim3(1), dim3(1), 0, stream, sc.d_mb, token);
+  LSR_HIP(hipGetLastError());
+  return wait_mailbox_word(&sc.mb.p->tf_token, token, stream, sc.wait_mode, "sensor-frame transform");
+}
+
 int pc2_ingest(const void* d_data, int step, int ox, int oy, int oz, int oi, size_t n, bool do_range, double rmin, double rmax,
-               DeviceCloud& out, BuildScratch& sc, hipStream_t stream) {
+               DeviceCloud& out, BuildScratch& sc, hipStream_t stream, const SensorTf12* tf) {
   int st = out.resize(n, oi >= 0);
   if (st) return st;
   if (n == 0) return LSR_OK;
@@ -420,8 +491,12 @@ int pc2_ingest(const void* d_data, int step, int ox, int oy, int oz, int oi, siz
   unsigned int token = ++sc.token;
   if (token == 0) token = ++sc.token;
   const int nb = std::max(1, std::min((int)((n + 1023) / 1024), BBOX_MAX_PARTS));
-  hipLaunchKernelGGL(pc2_ingest_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned char*)d_data, step, ox, oy, oz, oi, (int)n, out.x(),
-                     out.y(), out.z(), out.i(), do_range ? 1 : 0, rmin, rmax, sc.bbox_dev.p, sc.d_mb, token);
+  if (tf)
+    hipLaunchKernelGGL(pc2_ingest_kernel<true>, dim3(nb), dim3(256), 0, stream, (const unsigned char*)d_data, step, ox, oy, oz, oi, (int)n, out.x(),
+                       out.y(), out.z(), out.i(), do_range ? 1 : 0, rmin, rmax, sc.bbox_dev.p, sc.d_mb, token, *tf);
+  else
+    hipLaunchKernelGGL(pc2_ingest_kernel<false>, dim3(nb), dim3(256), 0, stream, (const unsigned char*)d_data, step, ox, oy, oz, oi, (int)n, out.x(),
+                       out.y(), out.z(), out.i(), do_range ? 1 : 0, rmin, rmax, sc.bbox_dev.p, sc.d_mb, token, SensorTf12{});
   LSR_HIP(hipGetLastError());
   sc.bbox_parts = nb;
   sc.bbox_token = token;

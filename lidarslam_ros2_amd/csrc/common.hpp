@@ -204,6 +204,7 @@ struct BuildMailbox {
   unsigned int vg_flags;      // VG_FLAG_*
   unsigned int vg_finite;     // finite points of the input
   unsigned int vg_bits;       // bits of the largest key (the next call on this scratch plans its sort with it)
+  unsigned int tf_token;      // pc2_transform: the records of the last sensor-frame transform are complete
 };
 constexpr unsigned int VG_FLAG_OVERFLOW = 1u;   // leaf index space beyond int32 (PCL: "Leaf size is too small for the input dataset")
 constexpr unsigned int VG_FLAG_REPLAN = 2u;     // the keys need more bits than the sort was planned for: run again with exact dimensions

@@ -31,8 +31,9 @@ int upload_cloud(lsr_handle h, const void* pts, size_t stride, size_t n, bool on
 
 // A PointCloud2 payload (or strided xyz records: a payload without intensity) -> SoA planes through pc2_ingest: ONE launch that also applies
 // the frontend's range filter (do_range) and leaves the bounding-box records for what follows
+// (tf: the payload is in the sensor frame and is moved into the robot frame as it is read, lsr_set_input_source_pc2_tf)
 int ingest_pc2(lsr_handle h, const void* data, size_t n, const lsr_pc2_layout* L, bool on_device, bool do_range, double rmin, double rmax,
-               DeviceCloud& out) {
+               DeviceCloud& out, const SensorTf12* tf = nullptr) {
   if (n > 0 && !data) { set_last_error("null PointCloud2 data"); return LSR_ERR_INVALID_ARGUMENT; }
   if (n > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
   const void* d = data;
@@ -43,7 +44,7 @@ int ingest_pc2(lsr_handle h, const void* data, size_t n, const lsr_pc2_layout* L
     d = h->staging.p;
   }
   return pc2_ingest(d, (int)L->point_step, (int)L->offset_x, (int)L->offset_y, (int)L->offset_z, L->offset_intensity, n, do_range, rmin, rmax,
-                    out, h->scratch, h->stream);
+                    out, h->scratch, h->stream, tf);
 }
 
 int set_target_impl(lsr_handle h, const void* pts, size_t stride, size_t n, bool on_device) {
@@ -441,12 +442,21 @@ int lsr_voxel_grid_filter(lsr_handle h, const void* pts, size_t stride_bytes, si
 
 int lsr_set_input_source_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, double scan_min_range,
                              double scan_max_range, float vg_size_for_input, int on_device, size_t* n_out) {
+  return lsr_set_input_source_pc2_tf(h, data, n_points, layout, nullptr, scan_min_range, scan_max_range, vg_size_for_input, on_device, n_out);
+}
+
+// the same from a payload in the SENSOR frame (tf2::doTransform, scanmatcher_component.cpp:195, applied as the records are read)
+int lsr_set_input_source_pc2_tf(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, const lsr_sensor_transform* tf,
+                                double scan_min_range, double scan_max_range, float vg_size_for_input, int on_device, size_t* n_out) {
   LSR_CHECK_HANDLE(h);
   int st = check_layout(layout);
   if (st) return st;
   if (!(vg_size_for_input > 0)) { set_last_error("leaf size must be > 0"); return LSR_ERR_INVALID_ARGUMENT; }
-  // payload -> planes + range filter + bounding-box records in one launch; the voxel filter behind it reads the records on the device
-  if ((st = ingest_pc2(h, data, n_points, layout, on_device != 0, true, scan_min_range, scan_max_range, h->raw))) return st;
+  SensorTf12 T;
+  if (tf && (st = lsr_sensor_transform_matrix(tf, T.m))) return st;
+  // payload -> planes (+ sensor -> robot frame) + range filter + bounding-box records in one launch; the voxel filter behind it reads
+  // the records on the device
+  if ((st = ingest_pc2(h, data, n_points, layout, on_device != 0, true, scan_min_range, scan_max_range, h->raw, tf ? &T : nullptr))) return st;
   if ((st = voxel_grid_filter(h->raw, vg_size_for_input, h->source, h->scratch, h->stream))) return st;
   return accept_source(h, n_out);
 }

@@ -228,8 +228,14 @@ void ndt_fill_align_constants(NdtState& st, const NdtParamsHost& prm, int n_poin
 int pc2_write(const DeviceCloud& in, void* d_data, int step, int ox, int oy, int oz, int oi, hipStream_t stream);
 // payload -> planes + the frontend's range filter (do_range) + the bounding-box pass in one launch; the box records wait in sc (host mailbox and
 // device memory) for cloud_bbox_end / voxel_grid_filter
+// tf (nullable): the scan is in the sensor frame; every point is moved by it as it is read, before the range filter and the box
+struct SensorTf12 { float m[12]; };   // rows 0-2 of the sensor -> robot matrix, row-major (lsr_sensor_transform_matrix)
 int pc2_ingest(const void* d_data, int step, int ox, int oy, int oz, int oi, size_t n, bool do_range, double rmin, double rmax,
-               DeviceCloud& out, BuildScratch& sc, hipStream_t stream);
+               DeviceCloud& out, BuildScratch& sc, hipStream_t stream, const SensorTf12* tf = nullptr);
+// tf2::doTransform on a payload, records -> records (d_in == d_out or disjoint).  wait: return when the records are complete for a
+// reader on any stream (the mailbox word of sc; no device-to-host copy, no stream synchronisation); else the launch is only enqueued.
+int pc2_transform(const void* d_in, void* d_out, int step, int ox, int oy, int oz, size_t n, const SensorTf12& tf, BuildScratch& sc,
+                  hipStream_t stream, bool wait);
 // N1: pcl::VoxelGrid::filter on the device (centroid per leaf, leaf-index order).
 int voxel_grid_filter(const DeviceCloud& cloud, float leaf, DeviceCloud& out, BuildScratch& sc, hipStream_t stream);
 int interleave(const DeviceCloud& in, void* d_out, size_t stride_bytes, hipStream_t stream);

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include "xform_ref.hpp"
+
 namespace lsr {
 
 // fp32 rotation block of (Translation * Rx * Ry * Rz) from the six float sines / cosines, the way the reference composes
@@ -43,17 +45,7 @@ __host__ __device__ inline void T12_to_colmajor16(const float* T, float* M) {
 // fuses a product with the addition that consumes it wherever its scheduler likes — differently in two kernels that inline the
 // same function (round 3's ISA: xform_ref came out as one fma in one row and two in another) — so the only fused operations
 // here are the explicit fmaf() calls, and a point's 29 terms are the same bits in every kernel variant and in the host emulation.
-//
-// Point transform in the REFERENCE's rounding order — pcl::transformPointCloud: ((m00 x + m01 y) + m02 z) + m03, every product
-// and sum rounded to fp32, no fused multiply-add.  The order matters more than it looks: a coordinate of ~50 m carries an
-// fp32 rounding error of ~2e-6 m, q = x' - mean is ~1 m, and the gradient of a pass moves by 3e-7 (relative) between this
-// order and an fmaf chain — enough to send a registration that walks thirty clamped 0.1 m steps along an ill-conditioned
-// Newton direction (BASELINE cfg 4, candidate 21) 2.4 mm away from the reference's result (tests/test_ndt_host_emu_cpu.py).
-__device__ __forceinline__ float xform_ref(const float a, const float b, const float c, const float d, const float x, const float y,
-                                           const float z) {
-#pragma clang fp contract(off)
-  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a, x), __fmul_rn(b, y)), __fmul_rn(c, z)), d);
-}
+// (The point transform itself, xform_ref, lives in xform_ref.hpp: the sensor-frame transform of the raw scan shares it.)
 
 // expf of the device library (OCML) without its two range guards: x * log2(e) split into a rounded product and its error,
 // the integer part by rndne, 2^fraction by v_exp_f32, the integer part back by ldexp — operation for operation what expf()

@@ -11,6 +11,10 @@ tests/test_frontend_stream_gpu.py) and — through an adapter with the same meth
     use_imu                      (:204-208) the raw payload is de-skewed once, on the device, before anything else reads it
                                  (deskewPointCloud2); the de-skewed records feed the scan path AND the map side, as `tmp_ptr` does;
                                  IMU messages arrive through receive_imu (:501-527)
+    sensor mount                 (:188-199) a payload in the sensor frame is moved into the robot frame first: inside the ingest launch of
+                                 the scan side and of the `mapper` (setInputSourcePointCloud2(sensor_transform=...)), by
+                                 transformPointCloud2 in front of the de-skew (use_imu) and on the host map path's copy
+    use_odom                     (:333-348) the guess of align is odomGuess(previous pose, previous odometry, odometry of this scan)
     registration_method "GICP"   the same loop; the assembled window is put through VoxelGrid(vg_size_for_input) before setInputTarget
                                  (:308-316): setInputTargetFramesFiltered + prepareTarget (the target's covariances) on the map side
     map_array                    (optional) the lidarslam_msgs/MapArray updateMap keeps (:466-481): every keyframe with the pose the message
@@ -70,6 +74,11 @@ class FrontendParams:   # scanmatcher_component.cpp:36-60 (declare_parameter def
     gicp_solver: str = "gauss_newton"  # GICP mode: the inner optimiser of `reg` — "gauss_newton", or "bfgs" (the reference's own schedule)
     use_imu: bool = False              # :78 — de-skew the raw scan with the IMU queue before the range filter (:204-208)
     scan_period: float = 0.1           # :80 — lidar_undistortion_.setScanPeriod
+    # :193-195 — lookupTransform(robot_frame_id_, msg->header.frame_id): where the sensor sits on the robot (mapping_car.launch.py:28
+    # mounts it at 1.2 0 2.0).  The identity (the default) means the payloads are in the robot frame already: no transform is made
+    sensor_translation: tuple = (0.0, 0.0, 0.0)
+    sensor_rotation_xyzw: tuple = (0.0, 0.0, 0.0, 1.0)
+    use_odom: bool = False             # :333-348 — the alignment guess follows the odometry between two scans (receive_cloud's `odom`)
 
 
 @dataclass
@@ -131,6 +140,11 @@ class FrontendReplay:
         self.submaps: list = []          # [(payload as given to setInputTargetFrames, pose 4x4 f64)]
         self.pose = np.eye(4)
         self.key_position = np.zeros(3)
+        t, q = tuple(float(v) for v in self.p.sensor_translation), tuple(float(v) for v in self.p.sensor_rotation_xyzw)
+        if len(t) != 3 or len(q) != 4:
+            raise ValueError("sensor_translation is x y z, sensor_rotation_xyzw a quaternion x y z w")
+        self._mount = None if (t, q) == ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0)) else (t, q)
+        self._previous_odom = np.eye(4, dtype=np.float32)   # previous_odom_mat_
         if self.p.use_imu:
             self.reg.imuReset(self.p.scan_period)
 
@@ -156,6 +170,7 @@ class FrontendReplay:
         self.pose = np.asarray(pose0, np.float64)
         self.key_position = np.asarray(frame_poses[-1], np.float64)[:3, 3].copy()
         self._n_scans = 0
+        self._previous_odom = np.eye(4, dtype=np.float32)
 
     def close(self):
         """Drains a pending update and stops the worker thread."""
@@ -184,21 +199,25 @@ class FrontendReplay:
         if self.builder is not None:
             self.reg.shareTargetOf(self.builder)
 
-    def _update_job(self, payload, n_points, payload_host, T, trans: float = 0.0):
-        """updateMap (:436-481) up to and including the target of the next scans; -> seconds."""
+    def _update_job(self, payload, n_points, payload_host, T, trans: float = 0.0, mount=None):
+        """updateMap (:436-481) up to and including the target of the next scans; -> seconds.  `mount`: the payload is still in the
+        sensor frame (a mounted sensor without IMU: the scan side moved it inside its ingest) and is moved here the same way."""
         step, offs = PC2_XYZI
         t2 = time.perf_counter()
         if self.mapper is not None and hasattr(payload, "is_cuda") and payload.is_cuda:
-            # the whole map side on the device: range filter + VoxelGrid(vg_size_for_map) into the mapper's source slot, from there
-            # into a keyframe buffer in HBM (lsr_set_input_source_pc2 + lsr_get_source_pc2_device)
+            # the whole map side on the device: (sensor -> robot frame +) range filter + VoxelGrid(vg_size_for_map) into the mapper's
+            # source slot, from there into a keyframe buffer in HBM (lsr_set_input_source_pc2 / _tf + lsr_get_source_pc2_device)
+            kw = {} if mount is None else {"sensor_transform": mount}
             self.mapper.setInputSourcePointCloud2(payload, n_points, step, offs, self.p.scan_min_range, self.p.scan_max_range,
-                                                  self.p.vg_size_for_map)
+                                                  self.p.vg_size_for_map, **kw)
             keyframe = self.mapper.getInputSourceDeviceRecords()
         else:
             src = payload if payload_host is None else payload_host
             if hasattr(src, "is_cuda") and src.is_cuda:
                 src = src.cpu().numpy()      # (a de-skewed device payload and no mapper object: the host-side filter needs a copy)
             host = np.asarray(src).reshape(n_points, step)
+            if mount is not None:            # doTransform (:195) of the host copy, ahead of the range mask as in the callback
+                host = (self.builder or self.reg).transformPointCloud2(host, n_points, step, offs, mount[0], mount[1]).reshape(n_points, step)
             # updateMap filters the cloud the callback received, i.e. AFTER the subscription's range filter (:210-218: horizontal range,
             # open interval, in double) — a host-side mask here, as in the reference
             xy = host[:, :8].copy().view(np.float32).astype(np.float64)
@@ -242,23 +261,42 @@ class FrontendReplay:
         out.swap_at.append(self._n_scans)
         self._pending = None
 
-    def receive_cloud(self, payload, n_points: int, out: FrontendResult, payload_host=None, scan_time: Optional[float] = None):
-        """One LiDAR message.  `payload`: the raw PointCloud2 data (host array or CUDA tensor); `payload_host`: a host copy for the map
-        update (the reference's callback holds the cloud on the host anyway); defaults to `payload`.  `scan_time`: the message's
-        header stamp [s]; needed with use_imu, where the payload is de-skewed first and the de-skewed records replace it for
-        everything that follows (the host copy included: the map side reads them back when it needs one)."""
+    def receive_cloud(self, payload, n_points: int, out: FrontendResult, payload_host=None, scan_time: Optional[float] = None, odom=None):
+        """One LiDAR message.  `payload`: the raw PointCloud2 data (host array or CUDA tensor), in the sensor frame when the parameters
+        name a mount; `payload_host`: a host copy for the map update (the reference's callback holds the cloud on the host anyway);
+        defaults to `payload`.  `scan_time`: the message's header stamp [s]; needed with use_imu, where the payload is (moved into
+        the robot frame and) de-skewed first and the de-skewed records replace it for everything that follows (the host copy
+        included: the map side reads them back when it needs one).  `odom`: the 4x4 odom_frame -> robot_frame of the scan's stamp
+        (:336-343); needed with use_odom — the reference logs a failed lookup and goes on with a default-constructed transform, which
+        is not reproduced: ValueError."""
         step, offs = PC2_XYZI
+        if self.p.use_imu and scan_time is None:
+            raise ValueError("use_imu needs the scan's header stamp (scan_time)")
+        if self.p.use_odom and odom is None:
+            raise ValueError("use_odom needs the odometry of the scan's stamp (odom)")
         t0 = time.perf_counter()
+        mount = self._mount
         if self.p.use_imu:
-            if scan_time is None:
-                raise ValueError("use_imu needs the scan's header stamp (scan_time)")
-            payload, _ = self.reg.deskewPointCloud2(payload, n_points, step, offs, scan_time)
+            if mount is not None:        # :188-208 — doTransform, then adjustDistortion on the transformed cloud (in place: the buffer is ours)
+                payload = self.reg.transformPointCloud2(payload, n_points, step, offs, mount[0], mount[1])
+                payload, _ = self.reg.deskewPointCloud2(payload, n_points, step, offs, scan_time, out=payload)
+                mount = None
+            else:
+                payload, _ = self.reg.deskewPointCloud2(payload, n_points, step, offs, scan_time)
             payload_host = None
         if self.async_update:
             self._settle(out)            # inside the scan's clock: what the callback really waits
+        # without IMU a mounted sensor's payload is moved inside the ingest launch (lsr_set_input_source_pc2_tf): no pass of its own
+        kw = {} if mount is None else {"sensor_transform": mount}
         kept = self.reg.setInputSourcePointCloud2(payload, n_points, step, offs, self.p.scan_min_range, self.p.scan_max_range,
-                                                  self.p.vg_size_for_input)
-        self.reg.align(self.pose.astype(np.float32))
+                                                  self.p.vg_size_for_input, **kw)
+        guess = self.pose.astype(np.float32)
+        if self.p.use_odom:              # :333-348
+            from .registration import odomGuess
+            odom = np.asarray(odom, np.float64).astype(np.float32)    # odom_affine.matrix().cast<float>()
+            guess = odomGuess(guess, self._previous_odom, odom)
+            self._previous_odom = odom
+        self.reg.align(guess)
         T = np.asarray(self.reg.getFinalTransformation(), np.float64)
         t1 = time.perf_counter()
         self.pose = T
@@ -270,7 +308,7 @@ class FrontendReplay:
         if self._pending is None and trans >= self.p.trans_for_mapupdate:
             self.key_position = T[:3, 3].copy()
             out.update_at.append(len(out.poses) - 1)
-            job = (lambda p=payload, n=n_points, h=payload_host, TT=T.copy(), d=trans: self._update_job(p, n, h, TT, d))
+            job = (lambda p=payload, n=n_points, h=payload_host, TT=T.copy(), d=trans, m=mount: self._update_job(p, n, h, TT, d, m))
             if self.async_update:
                 if self._pool is None:
                     from concurrent.futures import ThreadPoolExecutor

@@ -75,6 +75,33 @@ def _col16_to_mat(v) -> np.ndarray:
     return np.asarray(v, np.float32).reshape(4, 4).T.copy()
 
 
+def _sensor_transform(translation, rotation_xyzw) -> "capi.SensorTransform":
+    t, q = np.asarray(translation, np.float64).reshape(-1), np.asarray(rotation_xyzw, np.float64).reshape(-1)
+    if t.shape != (3,) or q.shape != (4,):
+        raise ValueError("a sensor transform is a translation (3,) and a quaternion x y z w (4,)")
+    return capi.SensorTransform((C.c_double * 3)(*t), (C.c_double * 4)(*q))
+
+
+def sensorTransformMatrix(translation, rotation_xyzw) -> np.ndarray:
+    """The (3, 4) fp32 matrix the kernels move a sensor-frame point with (lsr_sensor_transform_matrix): the double 4x4 of
+    lookupTransform(robot_frame, msg.frame_id) (scanmatcher_component.cpp:193-194), quaternion not normalised, cast element by element."""
+    tf = _sensor_transform(translation, rotation_xyzw)
+    out = np.zeros(12, np.float32)
+    capi.check(capi.load().lsr_sensor_transform_matrix(C.byref(tf), out.ctypes.data_as(C.POINTER(C.c_float))), "sensorTransformMatrix")
+    return out.reshape(3, 4)
+
+
+def odomGuess(sim_trans, previous_odom, odom) -> np.ndarray:
+    """receiveCloud's use_odom guess (scanmatcher_component.cpp:333-348) through lsr_odom_guess: sim_trans when previous_odom is
+    exactly the identity, else sim_trans * previous_odom^-1 * odom (double arithmetic on the fp32 inputs, rounded once).  4x4 in,
+    4x4 fp32 out."""
+    fp = C.POINTER(C.c_float)
+    s, p, o = (_mat_to_col16(M) for M in (sim_trans, previous_odom, odom))
+    g = np.zeros(16, np.float32)
+    capi.check(capi.load().lsr_odom_guess(s.ctypes.data_as(fp), p.ctypes.data_as(fp), o.ctypes.data_as(fp), g.ctypes.data_as(fp)), "odomGuess")
+    return _col16_to_mat(g)
+
+
 def _order_after_torch(reg, cloud):
     """A CUDA tensor may be the result of kernels still running on torch's current stream: make the handle's stream wait
     for that stream (lsr_wait_stream: event record + stream wait, no host wait) before the core reads the tensor."""
@@ -236,9 +263,12 @@ class Registration:
         return capi.Pc2Layout(int(point_step), int(ox), int(oy), int(oz), int(-1 if oi is None else oi))
 
     def setInputSourcePointCloud2(self, data, n_points: int, point_step: int, offsets, scan_min_range: float, scan_max_range: float,
-                                  vg_size_for_input: float) -> int:
+                                  vg_size_for_input: float, sensor_transform=None) -> int:
         """pcl::fromROSMsg + range filter + VoxelGrid + setInputSource from a raw PointCloud2 `data` buffer (bytes / uint8 numpy
-        array / CUDA uint8 tensor); offsets = (x, y, z, intensity or None) in bytes.  Returns the number of points kept."""
+        array / CUDA uint8 tensor); offsets = (x, y, z, intensity or None) in bytes.  Returns the number of points kept.
+        sensor_transform: (translation xyz, rotation xyzw) of lookupTransform(robot_frame, msg.frame_id) — the payload is in the sensor
+        frame and is moved into the robot frame as it is read (tf2::doTransform, scanmatcher_component.cpp:195), before the range
+        filter; None: the payload is in the robot frame already."""
         lay = self._layout(point_step, offsets)
         n_out = C.c_size_t()
         if _is_torch_cuda(data):
@@ -247,10 +277,38 @@ class Registration:
         else:
             keep = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
             ptr, dev = C.c_void_p(keep.ctypes.data), 0
-        capi.check(self._lib.lsr_set_input_source_pc2(self._h, ptr, int(n_points), C.byref(lay), float(scan_min_range), float(scan_max_range),
-                                                      C.c_float(vg_size_for_input), dev, C.byref(n_out)), "setInputSourcePointCloud2")
+        if sensor_transform is None:
+            st = self._lib.lsr_set_input_source_pc2(self._h, ptr, int(n_points), C.byref(lay), float(scan_min_range), float(scan_max_range),
+                                                    C.c_float(vg_size_for_input), dev, C.byref(n_out))
+        else:
+            tf = _sensor_transform(*sensor_transform)
+            st = self._lib.lsr_set_input_source_pc2_tf(self._h, ptr, int(n_points), C.byref(lay), C.byref(tf), float(scan_min_range),
+                                                       float(scan_max_range), C.c_float(vg_size_for_input), dev, C.byref(n_out))
+        capi.check(st, "setInputSourcePointCloud2")
         self._n_source = int(n_out.value)
         return self._n_source
+
+    def transformPointCloud2(self, data, n_points: int, point_step: int, offsets, translation, rotation_xyzw, out=None):
+        """tf2::doTransform(*msg, transformed_msg, transform) on a raw PointCloud2 `data` buffer (scanmatcher_component.cpp:195), on the
+        device: x / y / z of every record moved by the transform (translation xyz, quaternion x y z w, not normalised), every other
+        byte copied.  `data`: uint8 numpy array / bytes (-> numpy array out) or CUDA uint8 tensor (-> CUDA tensor out, nothing leaves
+        HBM).  `out`: None = a new buffer, or the buffer to write (`data` itself: in place).  Returns the records."""
+        lay = self._layout(point_step, offsets)
+        tf = _sensor_transform(translation, rotation_xyzw)
+        if _is_torch_cuda(data):
+            import torch
+
+            if out is None:
+                out = torch.empty_like(data)
+            _order_after_torch(self, data)
+            src, dst, dev = C.c_void_p(data.data_ptr()), C.c_void_p(out.data_ptr()), 1
+        else:
+            keep = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
+            if out is None:
+                out = np.empty_like(keep)
+            src, dst, dev = C.c_void_p(keep.ctypes.data), C.c_void_p(out.ctypes.data), 0
+        capi.check(self._lib.lsr_transform_pc2(self._h, src, int(n_points), C.byref(lay), C.byref(tf), dev, dst), "transformPointCloud2")
+        return out
 
     # -- IMU de-skew of the raw scan (use_imu: scanmatcher_component.cpp:204-208, 501-527) ---------------------------
     def imuReset(self, scan_period: float = 0.1):
