@@ -39,10 +39,12 @@ typedef enum lsr_status {
   LSR_ERR_HIP = -3,             /* a HIP call failed; see lsr_last_error() */
   LSR_ERR_NO_TARGET = -4,       /* align/getFitnessScore before setInputTarget */
   LSR_ERR_NO_SOURCE = -5,       /* align/getFitnessScore before setInputSource */
-  LSR_ERR_NOT_IMPLEMENTED = -6, /* (no entry returns it at present; until round 6 the NDT neighbourhood KDTREE did) */
+  LSR_ERR_NOT_IMPLEMENTED = -6, /* a .pcd file the readers do not take: DATA binary_compressed, coordinates that are not 4-byte floats
+                                   (lsr_parse_pcd_header, lsr_decode_pcd, lsr_load_pcd; until round 6 the NDT neighbourhood KDTREE too) */
   LSR_ERR_INDEX_OVERFLOW = -7,  /* voxel index space exceeds int32 (PCL: "Leaf size is too small") */
   LSR_ERR_TOO_FEW_POINTS = -8,  /* GICP: cloud smaller than k_correspondences */
-  LSR_ERR_IO = -9               /* a file could not be opened or written (lsr_save_pcd_ascii); errno's text in lsr_last_error() */
+  LSR_ERR_IO = -9               /* a file could not be opened or written (lsr_save_pcd_ascii), opened or read (lsr_load_pcd,
+                                   lsr_set_input_target_pcd); errno's text in lsr_last_error() */
 } lsr_status;
 
 /* registration_method: scanmatcher_component.cpp:103-124, graph_based_slam_component.cpp:63-86 */
@@ -77,6 +79,10 @@ typedef enum lsr_key {
   LSR_PCD_FORMAT_MS = 12,             /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the formatting launches
                                          (length pass, scan, write pass; copies outside the brackets) of the last lsr_format_pcd_ascii /
                                          lsr_save_pcd_ascii / lsr_save_map_pcd_ascii on this object, summed over its pieces; else 0 */
+  LSR_PCD_PARSE_MS = 13,              /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the four launches (line
+                                         pass, scan, index pass, parse pass; copies outside the brackets) of the last lsr_decode_pcd /
+                                         lsr_load_pcd / lsr_set_input_target_pcd of an ASCII file on this object, summed over its
+                                         pieces; else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -124,6 +130,11 @@ typedef enum lsr_key {
   LSR_PCD_PIECE_RECORDS = 50,         /* records per piece of lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (64 .. 1 << 22, default 1 << 20): a
                                          piece is formatted and copied while the calling thread writes the one before it.  The file's
                                          bytes do not depend on it */
+  LSR_PCD_READ_PIECE_BYTES = 52,      /* bytes per piece of lsr_load_pcd / lsr_set_input_target_pcd (2048 .. 1 << 28, default 1 << 26): a piece
+                                         is read from the file while the one before it is parsed.  The records do not depend on it */
+  LSR_PCD_UNRESOLVED_TOKENS = 53,     /* read-only (lsr_get_i32): how many values of the last lsr_decode_pcd / lsr_load_pcd /
+                                         lsr_set_input_target_pcd on this object the device left to the C library's strtof (0 for every
+                                         text whose values have at most 19 significant digits) */
   LSR_GICP_SOLVER = 51                /* GICP inner optimiser (lsr_gicp_solver): LSR_GICP_GAUSS_NEWTON (default) or LSR_GICP_BFGS, the
                                          reference's own schedule (PCL's port of GSL vector_bfgs2: Fletcher line search, memoryless
                                          direction update, |g| < 1e-2 / max_inner_iterations / no progress).  Per object, no environment
@@ -573,6 +584,56 @@ int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t 
  * a map without any record is LSR_ERR_INVALID_ARGUMENT. */
 int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
                            int on_device, const double* poses16 /* nullable */, size_t* n_bytes);
+
+/* ---- reading .pcd files (the other half of map.pcd) ------------------------------------------ */
+/* PCD v0.7 files, DATA ascii and DATA binary, decoded on the device into records of an lsr_pc2_layout.  The semantics are RESTATED from
+ * knowledge of the format and of the C library, and unpinned, like SURVEY.md 9.10 (the reference has no reader: "map save only").
+ * Header (parsed on the host): lines ending in '\n'; `#` lines are comments; entries VERSION, FIELDS (or COLUMNS), SIZE, TYPE, COUNT
+ * (default all 1), WIDTH, HEIGHT (default 1), VIEWPOINT (default 0 0 0 1 0 0 0; returned, never applied), POINTS (default WIDTH * HEIGHT)
+ * and DATA; any other entry is passed over.  x, y, z are required, each SIZE 4 TYPE F COUNT 1; intensity is optional, of the same type
+ * (absent: the output field is +0).  Every other field, `_` included, in any order and with any COUNT, is skipped.
+ * ASCII body: lines end at '\n' (the last may lack one); values are separated by runs of blank, '\t' or '\r'; a line without a value is
+ * skipped; the first POINTS lines with a value are the points, in order, later lines are ignored; surplus values on a line are ignored.
+ * A point line is measured from its first byte that is not a blank: more than LSR_PCD_READ_MAX_LINE_BYTES bytes from there to its '\n' is an
+ * error.  A value is the decimal subset of what strtof takes in the C locale — [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)?,
+ * or [+-]? (inf | infinity | nan) in any letter case; hex floats, nan(...), trailing characters are refused — and becomes the fp32 nearest
+ * its exact value, ties to even, overflow to +-inf, gradual underflow through the denormals to +-0, -0 kept: glibc's strtof in the default
+ * rounding mode, by integer arithmetic on the device (values the device cannot decide, possible only beyond 19 significant digits, are
+ * settled by strtof on the host: LSR_PCD_UNRESOLVED_TOKENS).  nan, +nan = 0x7fc00000, -nan = 0xffc00000.
+ * Binary body: POINTS records of (sum of SIZE * COUNT) bytes from the byte behind the DATA line, the four fields copied bit for bit.
+ * Output: records of out_layout (rules and refusals of lsr_assemble_map's output layout; offset_intensity < 0 drops the intensity), every
+ * byte outside the fields zero.
+ * Errors: LSR_ERR_INVALID_ARGUMENT — a required entry missing or malformed ("header incomplete" when the bytes end before the DATA
+ * line), x, y or z absent, POINTS != WIDTH * HEIGHT, POINTS == 0; an ASCII line with fewer values than the fields demand, a value outside
+ * the grammar, a line too long, fewer point lines than POINTS (lsr_last_error() names the file byte offset of the line's first byte; of
+ * several bad lines the earliest); a binary body shorter than POINTS records; capacity_points below POINTS.  LSR_ERR_NOT_IMPLEMENTED —
+ * DATA binary_compressed; x, y, z or intensity not a 4-byte float.  LSR_ERR_INDEX_OVERFLOW — more than INT32_MAX points. */
+#define LSR_PCD_READ_MAX_LINE_BYTES 1024
+typedef struct lsr_pcd_info {
+  uint64_t n_points, width, height, data_offset; /* data_offset: of the body's first byte */
+  uint32_t point_step;                           /* bytes of a binary record: the sum of SIZE * COUNT */
+  int32_t data_kind /* 0 ascii, 1 binary, 2 binary_compressed */, has_intensity, n_fields;
+  double viewpoint[7];
+} lsr_pcd_info;
+/* The header at the head of a file image (host memory; the image may be cut anywhere behind the DATA line).  Host only, no handle.  With
+ * DATA binary_compressed *info is filled (data_kind 2) and the status is LSR_ERR_NOT_IMPLEMENTED; no other error touches *info. */
+int lsr_parse_pcd_header(const void* bytes, size_t n_bytes, lsr_pcd_info* info);
+/* A whole file image (host pointer, or HIP device pointer with on_device != 0; any alignment) -> its records in out_records (host, or HIP
+ * device buffer with out_on_device != 0; 4-byte aligned) of capacity_points records; *n_out = POINTS.  The inverse of
+ * lsr_format_pcd_ascii.  out_records == NULL: only *n_out is set (out_layout and capacity_points are ignored).  A body of 2^32 bytes or
+ * more is LSR_ERR_INDEX_OVERFLOW: files of any size go through lsr_load_pcd.  No error touches out_records or *n_out.  What the object
+ * answers afterwards (target, source, final transformation, fitness) is unchanged. */
+int lsr_decode_pcd(lsr_handle h, const void* image, size_t n_bytes, int on_device, void* out_records, size_t capacity_points,
+                   const lsr_pc2_layout* out_layout, int out_on_device, size_t* n_out);
+/* The same from the file `path`, read in pieces of LSR_PCD_READ_PIECE_BYTES through two pinned buffers kept on the object: an ASCII piece
+ * is cut at its last '\n' and what lies behind it is carried into the next; the calling thread reads piece k + 1 while piece k is parsed on
+ * the object's stream; reading stops once POINTS lines are in.  The records do not depend on the piece size.  LSR_ERR_IO, with errno's
+ * text in lsr_last_error(), when the file cannot be opened or read. */
+int lsr_load_pcd(lsr_handle h, const char* path, void* out_records, size_t capacity_points, const lsr_pc2_layout* out_layout,
+                 int out_on_device, size_t* n_out);
+/* setInputTarget from a file: lsr_load_pcd into a device buffer of pcl::PointXYZI records {32; 0, 4, 8, 16} kept on the object, then
+ * lsr_set_input_target_device over that buffer — the same target, bit for bit, as those two calls made by hand.  *n_points = POINTS. */
+int lsr_set_input_target_pcd(lsr_handle h, const char* path, size_t* n_points);
 
 /* ---- pose-graph optimisation --------------------------------------------- */
 /* The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319): g2o's VertexSE3 / EdgeSE3 graph with identity

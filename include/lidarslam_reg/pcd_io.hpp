@@ -1,5 +1,6 @@
 // lidarslam_reg/pcd_io.hpp — header-only helpers over lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (lidarslam_reg.h): map.pcd written
-// from the device, the bytes pcl::io::savePCDFileASCII writes.
+// from the device, the bytes pcl::io::savePCDFileASCII writes — and over lsr_load_pcd / lsr_set_input_target_pcd: such a file (or any
+// PCD v0.7 file, DATA ascii or binary, with float x y z [intensity]) read back on the device.
 //
 //   graph_based_slam/src/graph_based_slam_component.cpp:369   if (do_save_map) {pcl::io::savePCDFileASCII("map.pcd", *map_ptr);} // too heavy
 //
@@ -64,6 +65,39 @@ inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<
     std::memcpy(poses16.data() + 16 * i, M.data(), 16 * sizeof(double));
   }
   return saveMapPCD(h, path, submaps, poses16.data(), submaps_on_device);
+}
+
+// pcl::io::loadPCDFile(path, cloud) for the fields x y z [intensity]: the file's records, in `layout`, into `payload` (resized to
+// n * point_step bytes; a PointCloud2's data).  The text is parsed on the device while this thread reads the file.  Reports like the
+// save helpers (stderr, false); on failure `payload` is left as it was.  n_points (nullable) receives the count.
+inline bool loadPCDFile(lsr_handle h, const std::string& path, std::vector<uint8_t>& payload, const lsr_pc2_layout& layout = pcdPointXYZILayout(),
+                        size_t* n_points = nullptr) {
+  size_t n = 0;
+  int st = lsr_load_pcd(h, path.c_str(), nullptr, 0, nullptr, 0, &n);
+  std::vector<uint8_t> records;
+  if (st == LSR_OK) {
+    records.resize(n * layout.point_step);
+    st = lsr_load_pcd(h, path.c_str(), records.data(), n, &layout, 0, &n);
+  }
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::loadPCDFile] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  payload.swap(records);
+  if (n_points) *n_points = n;
+  return true;
+}
+
+// registration->setInputTarget(map) with the map in a .pcd file: the records never visit the host.  n_points (nullable) receives the count.
+inline bool setInputTargetPCD(lsr_handle h, const std::string& path, size_t* n_points = nullptr) {
+  size_t n = 0;
+  const int st = lsr_set_input_target_pcd(h, path.c_str(), &n);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::setInputTargetPCD] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_points) *n_points = n;
+  return true;
 }
 
 }  // namespace lidarslam_reg

@@ -22,6 +22,9 @@ KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
  EUCLIDEAN_FITNESS_EPSILON, GICP_EPSILON, MAP_ASSEMBLY_MS, POSE_GRAPH_BAND_SOLVE_MS, POSE_GRAPH_DENSE_MS,
  POSE_GRAPH_COMBINE_MS) = range(12)
 PCD_FORMAT_MS, PCD_PIECE_RECORDS = 12, 50
+PCD_PARSE_MS, PCD_READ_PIECE_BYTES, PCD_UNRESOLVED_TOKENS = 13, 52, 53
+PCD_READ_MAX_LINE_BYTES = 1024
+ERR_NOT_IMPLEMENTED, ERR_INDEX_OVERFLOW = -6, -7
 ERR_IO = -9
 PCD_ASCII_MAX_LINE_BYTES, PCD_ASCII_MAX_HEADER_BYTES = 60, 256
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
@@ -45,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "lsr_assemble_map", "lsr_pose_graph_edges", "lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long",
     "lsr_format_pcd_ascii", "lsr_save_pcd_ascii", "lsr_save_map_pcd_ascii", "lsr_gicp_bfgs_trace",
     "lsr_sensor_transform_matrix", "lsr_transform_pc2", "lsr_set_input_source_pc2_tf", "lsr_odom_guess",
+    "lsr_parse_pcd_header", "lsr_decode_pcd", "lsr_load_pcd", "lsr_set_input_target_pcd",
 ]
 
 
@@ -95,6 +99,12 @@ class PoseGraphTrace(C.Structure):
 class Pc2Layout(C.Structure):
     _fields_ = [("point_step", C.c_uint32), ("offset_x", C.c_uint32), ("offset_y", C.c_uint32), ("offset_z", C.c_uint32),
                 ("offset_intensity", C.c_int32)]
+
+
+class PcdInfo(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("width", C.c_uint64), ("height", C.c_uint64), ("data_offset", C.c_uint64),
+                ("point_step", C.c_uint32), ("data_kind", C.c_int32), ("has_intensity", C.c_int32), ("n_fields", C.c_int32),
+                ("viewpoint", C.c_double * 7)]
 
 
 class DeskewInfo(C.Structure):
@@ -173,6 +183,10 @@ def load() -> C.CDLL:
     L.lsr_format_pcd_ascii.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_save_pcd_ascii.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_save_map_pcd_ascii.argtypes = [vp, C.c_char_p, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, C.POINTER(C.c_size_t)]
+    L.lsr_parse_pcd_header.argtypes = [vp, C.c_size_t, C.POINTER(PcdInfo)]
+    L.lsr_decode_pcd.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_load_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_set_input_target_pcd.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t)]
     L.lsr_pose_graph_edges.argtypes = [dp, C.c_int, C.c_int, C.POINTER(PoseEdge), C.c_size_t, C.POINTER(C.c_size_t)]
     for name in ("lsr_optimize_pose_graph", "lsr_optimize_pose_graph_long"):
         getattr(L, name).argtypes = [vp, dp, C.c_int, C.POINTER(PoseEdge), C.c_int, C.POINTER(PoseGraphParams), dp,

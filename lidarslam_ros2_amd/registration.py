@@ -565,6 +565,75 @@ class Registration:
             capi.check(self._lib.lsr_set_i32(self._h, capi.PCD_PIECE_RECORDS, int(records)), "pcdPieceRecords")
         return self._geti(capi.PCD_PIECE_RECORDS)
 
+    # -- reading .pcd files ----------------------------------------------------------------------------
+    def decodePCD(self, image, layout=PC2_XYZI):
+        """The records of a whole .pcd file image (PCD v0.7, DATA ascii or binary; the inverse of formatPCDASCII), decoded on the device
+        through lsr_decode_pcd.  `image`: bytes / uint8 numpy array (-> (n, point_step) uint8 numpy array) or CUDA uint8 tensor (-> CUDA
+        tensor, nothing leaves HBM).  `layout`: (point_step, (x, y, z, intensity or None)) of the records wanted."""
+        lay = self._layout(*layout)
+        step = int(layout[0])
+        if _is_torch_cuda(image):
+            if not image.is_contiguous() or image.element_size() != 1:
+                raise ValueError("image must be a contiguous uint8 buffer")
+            _order_after_torch(self, image)
+            ptr, size, dev, keep = image.data_ptr(), image.numel(), 1, image
+        else:
+            keep = np.frombuffer(image, np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else np.ascontiguousarray(image).reshape(-1).view(np.uint8)
+            ptr, size, dev = keep.ctypes.data, keep.size, 0
+        n = C.c_size_t()
+        capi.check(self._lib.lsr_decode_pcd(self._h, C.c_void_p(ptr), size, dev, None, 0, None, 0, C.byref(n)), "decodePCD")
+        if dev:
+            import torch
+
+            out = torch.empty((n.value, step), dtype=torch.uint8, device=torch.device("cuda", self._device))
+            _order_after_torch(self, out)
+            optr = out.data_ptr()
+        else:
+            out = np.zeros((n.value, step), np.uint8)
+            optr = out.ctypes.data
+        capi.check(self._lib.lsr_decode_pcd(self._h, C.c_void_p(ptr), size, dev, C.c_void_p(optr), n.value, C.byref(lay), dev, C.byref(n)),
+                   "decodePCD")
+        return out
+
+    def loadPCDFile(self, path, layout=PC2_XYZI, device=False):
+        """The records of the .pcd file `path` through lsr_load_pcd: read piece by piece by this thread while the device parses the
+        piece before.  -> (n, point_step) uint8: a numpy array, or with device=True a CUDA tensor."""
+        lay = self._layout(*layout)
+        step = int(layout[0])
+        n = C.c_size_t()
+        capi.check(self._lib.lsr_load_pcd(self._h, os.fsencode(path), None, 0, None, 0, C.byref(n)), "loadPCDFile")
+        if device:
+            import torch
+
+            out = torch.empty((n.value, step), dtype=torch.uint8, device=torch.device("cuda", self._device))
+            _order_after_torch(self, out)
+            optr = out.data_ptr()
+        else:
+            out = np.zeros((n.value, step), np.uint8)
+            optr = out.ctypes.data
+        capi.check(self._lib.lsr_load_pcd(self._h, os.fsencode(path), C.c_void_p(optr), n.value, C.byref(lay), 1 if device else 0, C.byref(n)),
+                   "loadPCDFile")
+        return out
+
+    def setInputTargetPCD(self, path) -> int:
+        """setInputTarget from a .pcd file (lsr_set_input_target_pcd): the file's records stay on the device.  Returns the point count."""
+        n = C.c_size_t()
+        capi.check(self._lib.lsr_set_input_target_pcd(self._h, os.fsencode(path), C.byref(n)), "setInputTargetPCD")
+        self._n_target = int(n.value)
+        self._keep["target"] = None
+        return self._n_target
+
+    def pcdReadPieceBytes(self, nbytes: Optional[int] = None) -> int:
+        """Bytes per piece of loadPCDFile / setInputTargetPCD (LSR_PCD_READ_PIECE_BYTES, 2048 .. 1 << 28): sets it when given, returns
+        the current value.  The records do not depend on it."""
+        if nbytes is not None:
+            capi.check(self._lib.lsr_set_i32(self._h, capi.PCD_READ_PIECE_BYTES, int(nbytes)), "pcdReadPieceBytes")
+        return self._geti(capi.PCD_READ_PIECE_BYTES)
+
+    def pcdUnresolvedTokens(self) -> int:
+        """Values of the last decodePCD / loadPCDFile / setInputTargetPCD the device left to the C library (LSR_PCD_UNRESOLVED_TOKENS)."""
+        return self._geti(capi.PCD_UNRESOLVED_TOKENS)
+
     def optimizePoseGraph(self, poses, edges, max_iterations: int = 10, band: int = 5):
         """The optimiser half of doPoseAdjustment (graph_based_slam_component.cpp:267-319) through lsr_optimize_pose_graph_long: g2o's
         VertexSE3 / EdgeSE3 graph (identity information, vertex 0 fixed) under its Levenberg-Marquardt controller, on this object's
