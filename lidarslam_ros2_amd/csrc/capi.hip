@@ -339,17 +339,17 @@ int lsr_align(lsr_handle h, const float* guess, float* final_transformation, lsr
   }
   if (st) return st;
   if (output_pts) {
-    if (out_stride_bytes < 12 || (out_stride_bytes % 4) != 0) { set_last_error("bad output stride"); return LSR_ERR_INVALID_ARGUMENT; }
+    if ((st = arg_error(check_stride_arg(out_stride_bytes, "out_stride_bytes")))) return st;
     // PCL's align() first copies the source records into `output` and then overwrites x, y, z with the transformed
     // coordinates; every other field (intensity, ...) stays.  Same here: only the 12 xyz bytes of each record are written,
     // whatever the caller put in the rest of the record survives (12 bytes per point cross PCIe, packed).
     const size_t n = h->source.n;
-    if ((st = h->staging.reserve(n * 12))) return st;
     if ((st = h->out_xyz.reserve(n * 3))) return st;
-    LSR_HIP(hipMemcpyAsync(h->d_T16.p, h->final_T, 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if ((st = transform_to_strided(h->source, h->d_T16.p, h->staging.p, 12, h->stream))) return st;
-    LSR_HIP(hipMemcpyAsync(h->out_xyz.p, h->staging.p, n * 12, hipMemcpyDeviceToHost, h->stream));
-    LSR_HIP(hipStreamSynchronize(h->stream));
+    if ((st = stage_out(h, h->out_xyz.p, n * 12, false, [&](unsigned char* d) -> int {
+          LSR_HIP(hipMemcpyAsync(h->d_T16.p, h->final_T, 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+          return transform_to_strided(h->source, h->d_T16.p, d, 12, h->stream);
+        })))
+      return st;
     unsigned char* o = static_cast<unsigned char*>(output_pts);
     for (size_t i = 0; i < n; i++) std::memcpy(o + i * out_stride_bytes, h->out_xyz.p + 3 * i, 12);
   }

@@ -16,7 +16,7 @@
 
 #include <algorithm>
 
-#include "handle.hpp"
+#include "api_internal.hpp"
 
 namespace lsr {
 
@@ -238,25 +238,10 @@ int deskew_run(DeskewState& S, const void* d_in, void* d_out, size_t n, int step
 
 using namespace lsr;
 
-namespace {
-int deskew_check_handle(lsr_handle h) {
-  if (!h) { set_last_error("null handle"); return LSR_ERR_INVALID_ARGUMENT; }
-  return LSR_OK;
-}
-int deskew_check_layout(const lsr_pc2_layout* L) {
-  if (!L || L->point_step < 12 || (L->point_step % 4) != 0) { set_last_error("PointCloud2 layout: point_step must be a multiple of 4 and >= 12"); return LSR_ERR_INVALID_ARGUMENT; }
-  const uint32_t offs[3] = {L->offset_x, L->offset_y, L->offset_z};
-  for (uint32_t o : offs)
-    if ((o % 4) != 0 || o + 4 > L->point_step) { set_last_error("PointCloud2 layout: x/y/z offsets must be 4-byte aligned and inside point_step"); return LSR_ERR_INVALID_ARGUMENT; }
-  return LSR_OK;
-}
-}  // namespace
-
 extern "C" {
 
 int lsr_imu_reset(lsr_handle h, double scan_period) {
-  int st = deskew_check_handle(h);
-  if (st) return st;
+  LSR_CHECK_HANDLE_NOT_NULL(h);   // the IMU entries touch no device: no DeviceGuard, no stream
   if (!(scan_period > 0.0)) { set_last_error("scan_period must be > 0"); return LSR_ERR_INVALID_ARGUMENT; }
   h->deskew.imu.reset(scan_period);
   h->deskew.trace_n = 0;
@@ -264,8 +249,7 @@ int lsr_imu_reset(lsr_handle h, double scan_period) {
 }
 
 int lsr_imu_push(lsr_handle h, const float* ang_vel3, const float* acc3, const float* quat_wxyz4, double stamp) {
-  int st = deskew_check_handle(h);
-  if (st) return st;
+  LSR_CHECK_HANDLE_NOT_NULL(h);
   if (!ang_vel3 || !acc3 || !quat_wxyz4) { set_last_error("null IMU sample"); return LSR_ERR_INVALID_ARGUMENT; }
   if (h->deskew.imu.push(ang_vel3, acc3, quat_wxyz4, stamp) != IMU_PUSH_OK) {
     set_last_error("IMU sample refused: its stamp is smaller than the previous sample's");
@@ -276,8 +260,7 @@ int lsr_imu_push(lsr_handle h, const float* ang_vel3, const float* acc3, const f
 
 int lsr_imu_receive(lsr_handle h, const double* orientation_xyzw4, const double* angular_velocity3, const double* linear_acceleration3,
                     double stamp) {
-  int st = deskew_check_handle(h);
-  if (st) return st;
+  LSR_CHECK_HANDLE_NOT_NULL(h);
   if (!orientation_xyzw4 || !angular_velocity3 || !linear_acceleration3) { set_last_error("null IMU message field"); return LSR_ERR_INVALID_ARGUMENT; }
   float ang[3], acc[3], quat[4];
   ImuQueue::sample_from_msg(orientation_xyzw4, angular_velocity3, linear_acceleration3, ang, acc, quat);
@@ -285,8 +268,7 @@ int lsr_imu_receive(lsr_handle h, const double* orientation_xyzw4, const double*
 }
 
 int lsr_imu_info(lsr_handle h, int32_t* info4) {
-  int st = deskew_check_handle(h);
-  if (st) return st;
+  LSR_CHECK_HANDLE_NOT_NULL(h);
   if (!info4) { set_last_error("null output"); return LSR_ERR_INVALID_ARGUMENT; }
   const ImuQueue& Q = h->deskew.imu;
   info4[0] = (int32_t)std::min<long long>(Q.count, INT32_MAX);
@@ -298,24 +280,12 @@ int lsr_imu_info(lsr_handle h, int32_t* info4) {
 
 int lsr_deskew_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, double scan_time, int on_device,
                    void* out_data, lsr_deskew_info* info) {
-  int st = deskew_check_handle(h);
+  LSR_CHECK_HANDLE(h);
+  // the intensity field is not looked at: every byte outside x / y / z is copied as it is, whatever the layout says about it
+  int st = arg_error(check_layout_xyz(layout));
   if (st) return st;
-  if ((st = deskew_check_layout(layout))) return st;
-  if (n_points > 0 && (!data || !out_data)) { set_last_error("null PointCloud2 data"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (n_points > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
-  if ((reinterpret_cast<size_t>(data) & 3) != 0 || (reinterpret_cast<size_t>(out_data) & 3) != 0) { set_last_error("PointCloud2 data must be 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
+  if ((st = arg_error(check_records_in_out(data, out_data, n_points, layout->point_step)))) return st;
   const size_t bytes = n_points * (size_t)layout->point_step;
-  if (data != out_data && bytes > 0) {   // equal or disjoint: the apply pass copies records workgroup by workgroup
-    const uintptr_t a = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(out_data);
-    if (a < b + bytes && b < a + bytes) { set_last_error("data and out_data overlap: they must be equal (in place) or disjoint"); return LSR_ERR_INVALID_ARGUMENT; }
-  }
-  DeviceGuard guard(h->device);
-  if (!guard.ok) { set_last_error("hipSetDevice failed"); return LSR_ERR_HIP; }
-  if (h->dep) {   // the object was part of a group launch on another stream: its own stream waits for that first
-    if (h->dep_stream != h->stream) LSR_HIP(hipStreamWaitEvent(h->stream, h->dep->ev, 0));
-    h->dep.reset();
-    h->dep_stream = nullptr;
-  }
   DeskewState& S = h->deskew;
   lsr_deskew_info I = {0, 0, -1, S.imu.last_iter};
   S.trace_n = 0;
@@ -338,20 +308,12 @@ int lsr_deskew_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc
   std::memset(&U.ctl, 0, sizeof(DeskewCtl));
   U.ctl.half_index = 0xFFFFFFFFu;
   U.ctl.m = S.imu.linearise(U.table);
-  const void* d_in = data;
-  void* d_out = out_data;
-  if (!on_device) {
-    if ((st = h->staging.reserve(bytes))) return st;
-    LSR_HIP(hipMemcpyAsync(h->staging.p, data, bytes, hipMemcpyHostToDevice, h->stream));
-    d_in = d_out = h->staging.p;
-  }
-  if ((st = deskew_run(S, d_in, d_out, n_points, (int)layout->point_step, (int)layout->offset_x, (int)layout->offset_y, (int)layout->offset_z,
-                       scan_time, h->scratch.wait_mode, h->stream)))
+  // device records: deskew_run has waited for the mailbox, the records are complete; host records: the copy down comes behind it
+  if ((st = records_in_records_out(h, data, out_data, bytes, on_device != 0, [&](const void* d_in, void* d_out) {
+        return deskew_run(S, d_in, d_out, n_points, (int)layout->point_step, (int)layout->offset_x, (int)layout->offset_y,
+                          (int)layout->offset_z, scan_time, h->scratch.wait_mode, h->stream);
+      })))
     return st;
-  if (!on_device) {
-    LSR_HIP(hipMemcpyAsync(out_data, h->staging.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    LSR_HIP(hipStreamSynchronize(h->stream));
-  }
   const DeskewMailbox& M = *S.mb.p;
   S.trace_n = n_points;
   S.trace_base = S.imu.last_iter;
@@ -365,10 +327,7 @@ int lsr_deskew_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc
 }
 
 int lsr_deskew_trace(lsr_handle h, float* rel_time, int32_t* slot, uint8_t* skipped) {
-  int st = deskew_check_handle(h);
-  if (st) return st;
-  DeviceGuard guard(h->device);
-  if (!guard.ok) { set_last_error("hipSetDevice failed"); return LSR_ERR_HIP; }
+  LSR_CHECK_HANDLE(h);
   DeskewState& S = h->deskew;
   const size_t n = S.trace_n;
   if (n == 0) return LSR_OK;

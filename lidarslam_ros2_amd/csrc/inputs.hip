@@ -10,22 +10,10 @@ using namespace lsr;
 namespace {
 
 int upload_cloud(lsr_handle h, const void* pts, size_t stride, size_t n, bool on_device, DeviceCloud& out) {
-  if (int st = check_stride(stride)) return st;
-  if (n > 0 && !pts) {
-    set_last_error("null point pointer");
-    return LSR_ERR_INVALID_ARGUMENT;
-  }
-  if (n > (size_t)INT32_MAX / 2) {
-    set_last_error("cloud too large");
-    return LSR_ERR_INVALID_ARGUMENT;
-  }
-  const void* d_aos = pts;
-  if (!on_device && n > 0) {
-    int st = h->staging.reserve(n * stride);
-    if (st) return st;
-    LSR_HIP(hipMemcpyAsync(h->staging.p, pts, n * stride, hipMemcpyHostToDevice, h->stream));
-    d_aos = h->staging.p;
-  }
+  int st;
+  if ((st = check_stride(stride)) || (st = arg_error(check_records(pts, n, INGEST_RECORD_LIMIT, false, "points")))) return st;
+  const void* d_aos = nullptr;
+  if ((st = stage_in(h, pts, n * stride, on_device, h->stream, &d_aos))) return st;
   return deinterleave(d_aos, stride, n, out, h->stream);
 }
 
@@ -34,15 +22,10 @@ int upload_cloud(lsr_handle h, const void* pts, size_t stride, size_t n, bool on
 // (tf: the payload is in the sensor frame and is moved into the robot frame as it is read, lsr_set_input_source_pc2_tf)
 int ingest_pc2(lsr_handle h, const void* data, size_t n, const lsr_pc2_layout* L, bool on_device, bool do_range, double rmin, double rmax,
                DeviceCloud& out, const SensorTf12* tf = nullptr) {
-  if (n > 0 && !data) { set_last_error("null PointCloud2 data"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (n > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
-  const void* d = data;
-  if (!on_device && n > 0) {
-    int st = h->staging.reserve(n * L->point_step);
-    if (st) return st;
-    LSR_HIP(hipMemcpyAsync(h->staging.p, data, n * L->point_step, hipMemcpyHostToDevice, h->stream));
-    d = h->staging.p;
-  }
+  int st = arg_error(check_records(data, n, INGEST_RECORD_LIMIT, false, "data"));
+  if (st) return st;
+  const void* d = nullptr;
+  if ((st = stage_in(h, data, n * L->point_step, on_device, h->stream, &d))) return st;
   return pc2_ingest(d, (int)L->point_step, (int)L->offset_x, (int)L->offset_y, (int)L->offset_z, L->offset_intensity, n, do_range, rmin, rmax,
                     out, h->scratch, h->stream, tf);
 }
@@ -107,30 +90,12 @@ int write_pc2_host(lsr_handle h, const DeviceCloud& cloud, void* out_data, size_
   *n_out = cloud.n;
   if (cloud.n > capacity) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
   if (cloud.n == 0) return LSR_OK;
-  const size_t bytes = cloud.n * L->point_step;
-  int st = h->staging.reserve(bytes);
-  if (st) return st;
-  LSR_HIP(hipMemsetAsync(h->staging.p, 0, bytes, h->stream));
-  if ((st = pc2_write(cloud, h->staging.p, (int)L->point_step, (int)L->offset_x, (int)L->offset_y, (int)L->offset_z, L->offset_intensity, h->stream)))
-    return st;
-  LSR_HIP(hipMemcpyAsync(out_data, h->staging.p, bytes, hipMemcpyDeviceToHost, h->stream));
-  LSR_HIP(hipStreamSynchronize(h->stream));
-  return LSR_OK;
+  return stage_out(h, out_data, cloud.n * L->point_step, true, [&](unsigned char* d) {
+    return pc2_write(cloud, d, (int)L->point_step, (int)L->offset_x, (int)L->offset_y, (int)L->offset_z, L->offset_intensity, h->stream);
+  });
 }
 
 }  // namespace
-
-int lsr::check_layout(const lsr_pc2_layout* L) {
-  if (!L || L->point_step < 12 || (L->point_step % 4) != 0) { set_last_error("PointCloud2 layout: point_step must be a multiple of 4 and >= 12"); return LSR_ERR_INVALID_ARGUMENT; }
-  const uint32_t offs[3] = {L->offset_x, L->offset_y, L->offset_z};
-  for (uint32_t o : offs)
-    if ((o % 4) != 0 || o + 4 > L->point_step) { set_last_error("PointCloud2 layout: x/y/z offsets must be 4-byte aligned and inside point_step"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (L->offset_intensity >= 0 && ((L->offset_intensity % 4) != 0 || (uint32_t)L->offset_intensity + 4 > L->point_step)) {
-    set_last_error("PointCloud2 layout: intensity offset must be 4-byte aligned and inside point_step (or < 0 for none)");
-    return LSR_ERR_INVALID_ARGUMENT;
-  }
-  return LSR_OK;
-}
 
 // Submap assembly + setInputTarget without a host round trip of the assembled cloud
 // (scanmatcher_component.cpp:449-464,307; graph_based_slam_component.cpp:208-227)
@@ -138,24 +103,16 @@ int lsr::check_layout(const lsr_pc2_layout* L) {
 int lsr::assemble_frames(lsr_handle h, int n_frames, const void* const* frames, const size_t* counts, size_t stride_bytes,
                          const float* poses16, bool on_device, DeviceCloud& out) {
   size_t total = 0, biggest = 0;
-  for (int f = 0; f < n_frames; f++) {
-    if (counts[f] > 0 && !frames[f]) { set_last_error("null frame pointer"); return LSR_ERR_INVALID_ARGUMENT; }
-    total += counts[f];
-    biggest = std::max(biggest, counts[f]);
-  }
-  if (total > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
-  int st = out.resize(total);
+  int st = arg_error(check_frame_list(n_frames, frames, counts, stride_bytes, poses16, &total, &biggest));
   if (st) return st;
+  if ((st = out.resize(total))) return st;
   if ((st = h->d_poses.reserve((size_t)n_frames * 16))) return st;
   LSR_HIP(hipMemcpyAsync(h->d_poses.p, poses16, sizeof(float) * 16 * n_frames, hipMemcpyHostToDevice, h->stream));
   if (!on_device && (st = h->staging.reserve(biggest * stride_bytes))) return st;
   size_t off = 0;
   for (int f = 0; f < n_frames; f++) {
-    const void* d_aos = frames[f];
-    if (!on_device && counts[f] > 0) {
-      LSR_HIP(hipMemcpyAsync(h->staging.p, frames[f], counts[f] * stride_bytes, hipMemcpyHostToDevice, h->stream));
-      d_aos = h->staging.p;
-    }
+    const void* d_aos = nullptr;
+    if ((st = stage_in_at(h, frames[f], counts[f] * stride_bytes, on_device, h->stream, 0, &d_aos))) return st;
     if ((st = transform_append(d_aos, stride_bytes, counts[f], h->d_poses.p + 16 * f, out, off, h->stream))) return st;
     if (!on_device) LSR_HIP(hipStreamSynchronize(h->stream));  // the staging buffer is reused by the next frame
     off += counts[f];
@@ -170,12 +127,10 @@ extern "C" {
 int lsr_set_input_target_frames(lsr_handle h, int n_frames, const void* const* frames, const size_t* counts, size_t stride_bytes,
                                 const float* poses16, int on_device) {
   LSR_CHECK_HANDLE(h);
-  if (n_frames <= 0 || !frames || !counts || !poses16 || stride_bytes < 12 || (stride_bytes % 4)) {
-    set_last_error("bad frame list");
-    return LSR_ERR_INVALID_ARGUMENT;
-  }
+  int st = arg_error(check_frame_list(n_frames, frames, counts, stride_bytes, poses16));   // before the object is touched
+  if (st) return st;
   auto t = fresh_target(h);
-  int st = assemble_frames(h, n_frames, frames, counts, stride_bytes, poses16, on_device != 0, t->cloud);
+  st = assemble_frames(h, n_frames, frames, counts, stride_bytes, poses16, on_device != 0, t->cloud);
   if (st) return st;
   t->n = t->cloud.n;
   h->target = t;
@@ -193,18 +148,10 @@ int lsr_set_input_target_frames_filtered(lsr_handle h, int n_frames, const void*
   LSR_CHECK_HANDLE(h);
   if (n_out) *n_out = 0;
   h->target.reset();   // on error the object keeps no target
-  if (n_frames <= 0 || !frames || !counts || !poses16 || stride_bytes < 12 || (stride_bytes % 4)) {
-    set_last_error("bad frame list");
-    return LSR_ERR_INVALID_ARGUMENT;
-  }
-  if (!(leaf > 0)) { set_last_error("leaf size must be > 0"); return LSR_ERR_INVALID_ARGUMENT; }
   size_t total = 0;
-  for (int f = 0; f < n_frames; f++) {
-    if (counts[f] > 0 && !frames[f]) { set_last_error("null frame pointer"); return LSR_ERR_INVALID_ARGUMENT; }
-    total += counts[f];
-  }
-  if (total > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
-  int st;
+  int st = arg_error(check_frame_list(n_frames, frames, counts, stride_bytes, poses16, &total));
+  if (st) return st;
+  if (!(leaf > 0)) { set_last_error("leaf size must be > 0"); return LSR_ERR_INVALID_ARGUMENT; }
   if ((st = h->h_frames.reserve((size_t)n_frames))) return st;
   if ((st = h->d_frames.reserve((size_t)n_frames))) return st;
   if (!on_device && (st = h->staging.reserve(total * stride_bytes))) return st;
@@ -215,11 +162,9 @@ int lsr_set_input_target_frames_filtered(lsr_handle h, int n_frames, const void*
   size_t off = 0;
   for (int f = 0; f < n_frames; f++) {   // host frames are staged back to back and go through the same launch
     FrameSlot& F = h->h_frames.p[f];
-    F.records = static_cast<const unsigned char*>(frames[f]);
-    if (!on_device) {
-      F.records = h->staging.p + off * stride_bytes;
-      if (counts[f] > 0) LSR_HIP(hipMemcpyAsync(h->staging.p + off * stride_bytes, frames[f], counts[f] * stride_bytes, hipMemcpyHostToDevice, h->stream));
-    }
+    const void* d_frame = nullptr;
+    if ((st = stage_in_at(h, frames[f], counts[f] * stride_bytes, on_device != 0, h->stream, off * stride_bytes, &d_frame))) return st;
+    F.records = static_cast<const unsigned char*>(d_frame);
     F.count = (int)counts[f];
     F.first_out = (int)off;
     F.first_slice = first_slice[f];
@@ -287,8 +232,7 @@ int lsr_set_input_target_batch(lsr_handle* handles, int count, const void* const
   std::vector<int> job_of((size_t)count, -1);
   for (int b = 0; b < count; b++) {   // stage 0: uploads (+ de-interleave and bounding boxes of the NDT members in group launches)
     lsr_handle h = handles[b];
-    if (counts[b] > 0 && !clouds[b]) { set_last_error("null point pointer"); return fail(LSR_ERR_INVALID_ARGUMENT); }
-    if (counts[b] > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return fail(LSR_ERR_INVALID_ARGUMENT); }
+    if ((st = arg_error(check_records(clouds[b], counts[b], INGEST_RECORD_LIMIT, false, "clouds[]")))) return fail(st);
     auto t = fresh_target(h);
     t->n = counts[b];
     h->target = t;
@@ -299,12 +243,8 @@ int lsr_set_input_target_batch(lsr_handle* handles, int count, const void* const
       continue;
     }
     if ((st = order_lead_after(lead_stream, h))) return fail(st);   // whatever this member still has in flight on its own stream comes first
-    const void* d_aos = clouds[b];
-    if (!on_device && counts[b] > 0) {
-      if ((st = h->staging.reserve(counts[b] * stride_bytes))) return fail(st);
-      if (hipMemcpyAsync(h->staging.p, clouds[b], counts[b] * stride_bytes, hipMemcpyHostToDevice, lead_stream) != hipSuccess) return fail(LSR_ERR_HIP);
-      d_aos = h->staging.p;
-    }
+    const void* d_aos = nullptr;
+    if ((st = stage_in(h, clouds[b], counts[b] * stride_bytes, on_device != 0, lead_stream, &d_aos))) return fail(st);
     job_of[b] = (int)jobs.size();
     jobs.push_back(TargetBuildJob{d_aos, stride_bytes, counts[b], &t->cloud, (float)h->ndt.resolution, &t->grid, &h->scratch, 0});
   }
@@ -353,10 +293,8 @@ int lsr_set_input_source_batch(lsr_handle* handles, int count, const void* const
   int st;
   if ((st = check_stride(stride_bytes))) return st;
   if ((st = check_batch_members(handles, count, false, true))) return st;
-  for (int b = 0; b < count; b++) {
-    if (counts[b] > 0 && !clouds[b]) { set_last_error("null point pointer"); return LSR_ERR_INVALID_ARGUMENT; }
-    if (counts[b] > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
-  }
+  for (int b = 0; b < count; b++)
+    if ((st = arg_error(check_records(clouds[b], counts[b], INGEST_RECORD_LIMIT, false, "clouds[]")))) return st;
   DeviceGuard guard(handles[0]->device);
   if (!guard.ok) { set_last_error("hipSetDevice failed"); return LSR_ERR_HIP; }
   hipStream_t lead_stream = handles[0]->stream;
@@ -372,15 +310,8 @@ int lsr_set_input_source_batch(lsr_handle* handles, int count, const void* const
   for (int b = 0; b < count; b++) {
     lsr_handle h = handles[b];
     if ((st = order_lead_after(lead_stream, h))) return fail(st);
-    const void* d_aos = clouds[b];
-    if (!on_device && counts[b] > 0) {
-      if ((st = h->staging.reserve(counts[b] * stride_bytes))) return fail(st);
-      if (hipMemcpyAsync(h->staging.p, clouds[b], counts[b] * stride_bytes, hipMemcpyHostToDevice, lead_stream) != hipSuccess) {
-        set_last_error("staging copy of a source failed");
-        return fail(LSR_ERR_HIP);
-      }
-      d_aos = h->staging.p;
-    }
+    const void* d_aos = nullptr;
+    if ((st = stage_in(h, clouds[b], counts[b] * stride_bytes, on_device != 0, lead_stream, &d_aos))) return fail(st);
     jobs[b] = DeinterleaveJob{d_aos, stride_bytes, counts[b], &h->source};
   }
   if ((st = deinterleave_group(jobs.data(), count, lead_stream))) return fail(st);
@@ -412,7 +343,6 @@ int lsr_set_input_source_frontend(lsr_handle h, const void* pts, size_t stride_b
   if (!(vg_size_for_input > 0)) { set_last_error("leaf size must be > 0"); return LSR_ERR_INVALID_ARGUMENT; }
   int st = check_stride(stride_bytes);
   if (st) return st;
-  if (n > 0 && !pts) { set_last_error("null point pointer"); return LSR_ERR_INVALID_ARGUMENT; }
   // strided xyz records are a PointCloud2 payload without an intensity field: the same one-launch ingest
   const lsr_pc2_layout rec_layout{(uint32_t)stride_bytes, 0u, 4u, 8u, -1};
   if ((st = ingest_pc2(h, pts, n, &rec_layout, on_device != 0, true, scan_min_range, scan_max_range, h->raw))) return st;
@@ -424,20 +354,17 @@ int lsr_set_input_source_frontend(lsr_handle h, const void* pts, size_t stride_b
 int lsr_voxel_grid_filter(lsr_handle h, const void* pts, size_t stride_bytes, size_t n, float leaf, void* out_pts,
                           size_t out_stride_bytes, size_t out_capacity, size_t* n_out) {
   LSR_CHECK_HANDLE(h);
-  if (!(leaf > 0) || !n_out || out_stride_bytes < 12 || (out_stride_bytes % 4)) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
-  int st = upload_cloud(h, pts, stride_bytes, n, false, h->raw);
+  if (!(leaf > 0) || !n_out) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
+  int st = arg_error(check_stride_arg(out_stride_bytes, "out_stride_bytes"));
+  if (st) return st;
+  st = upload_cloud(h, pts, stride_bytes, n, false, h->raw);
   if (st) return st;
   if ((st = voxel_grid_filter(h->raw, leaf, h->filtered, h->scratch, h->stream))) return st;
   *n_out = h->filtered.n;
   if (h->filtered.n > out_capacity) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
   if (h->filtered.n == 0) return LSR_OK;
-  const size_t bytes = h->filtered.n * out_stride_bytes;
-  if ((st = h->staging.reserve(bytes))) return st;
-  LSR_HIP(hipMemsetAsync(h->staging.p, 0, bytes, h->stream));
-  if ((st = interleave(h->filtered, h->staging.p, out_stride_bytes, h->stream))) return st;
-  LSR_HIP(hipMemcpyAsync(out_pts, h->staging.p, bytes, hipMemcpyDeviceToHost, h->stream));
-  LSR_HIP(hipStreamSynchronize(h->stream));
-  return LSR_OK;
+  return stage_out(h, out_pts, h->filtered.n * out_stride_bytes, true,
+                   [&](unsigned char* d) { return interleave(h->filtered, d, out_stride_bytes, h->stream); });
 }
 
 int lsr_set_input_source_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, double scan_min_range,
@@ -492,9 +419,9 @@ int lsr_get_source_pc2_device(lsr_handle h, void* d_out, size_t capacity_points,
 int lsr_voxel_grid_filter_pc2(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* in_layout, float leaf, void* out_data,
                               size_t capacity_points, const lsr_pc2_layout* out_layout, size_t* n_out) {
   LSR_CHECK_HANDLE(h);
-  int st = check_layout(in_layout);
+  int st = check_layout(in_layout, "in_layout");
   if (st) return st;
-  if ((st = check_layout(out_layout))) return st;
+  if ((st = check_layout(out_layout, "out_layout"))) return st;
   if (!(leaf > 0) || !n_out) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
   if ((st = ingest_pc2(h, data, n_points, in_layout, false, false, 0.0, 0.0, h->raw))) return st;
   if ((st = voxel_grid_filter(h->raw, leaf, h->filtered, h->scratch, h->stream))) return st;

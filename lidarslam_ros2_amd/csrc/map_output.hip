@@ -14,29 +14,17 @@ constexpr size_t MAP_STAGE_BYTES = (size_t)64 << 20;
 bool is_xyzi_layout(const lsr_pc2_layout* L) {
   return L->point_step == 32 && L->offset_x == 0 && L->offset_y == 4 && L->offset_z == 8 && L->offset_intensity == 16;
 }
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a_bytes > 0 && b_bytes > 0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
 
 int pcd_check_args(const void* data, size_t n, const lsr_pc2_layout* layout, PcdFields* F) {
-  if (!data) { set_last_error("null record pointer"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (!data) { set_last_error("data: null record pointer"); return LSR_ERR_INVALID_ARGUMENT; }
   int st = check_layout(layout);
   if (st) return st;
-  if ((uintptr_t)data & 3) { set_last_error("records are not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (n == 0) { set_last_error("an empty cloud has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (n > (size_t)INT32_MAX) { set_last_error("more than INT32_MAX records"); return LSR_ERR_INDEX_OVERFLOW; }
+  if (n == 0) { set_last_error("n_points: an empty cloud has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }   // PCL refuses it too
+  if ((st = arg_error(check_records(data, n, MAP_RECORD_LIMIT, true, "data")))) return st;
   F->step = (int)layout->point_step;
   F->n_fields = layout->offset_intensity >= 0 ? 4 : 3;
   F->off[0] = (int)layout->offset_x; F->off[1] = (int)layout->offset_y; F->off[2] = (int)layout->offset_z;
   F->off[3] = layout->offset_intensity >= 0 ? layout->offset_intensity : 0;
-  return LSR_OK;
-}
-// a bracket whose second event has completed
-int pcd_add_ms(hipEvent_t a, hipEvent_t b, double* ms) {
-  float t = 0.f;
-  LSR_HIP(hipEventElapsedTime(&t, a, b));
-  *ms += t;
   return LSR_OK;
 }
 int pcd_io_error(const char* what, const char* path) {
@@ -76,16 +64,9 @@ int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, c
                      size_t* first_record, size_t* n_out) {
   LSR_CHECK_HANDLE(h);
   if (!submaps || num_submaps <= 0 || !n_out) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
-  int st = check_layout(in_layout);
+  int st = check_layout(in_layout, "in_layout");
   if (st) return st;
-  if ((st = check_layout(out_layout))) return st;
-  {
-    const int64_t f[4] = {(int64_t)out_layout->offset_x, (int64_t)out_layout->offset_y, (int64_t)out_layout->offset_z,
-                          out_layout->offset_intensity >= 0 ? (int64_t)out_layout->offset_intensity : (int64_t)-1};
-    for (int a = 0; a < 4; a++)
-      for (int b = a + 1; b < 4; b++)
-        if (f[a] >= 0 && f[a] == f[b]) { set_last_error("PointCloud2 layout: output fields overlap"); return LSR_ERR_INVALID_ARGUMENT; }
-  }
+  if ((st = check_out_layout(out_layout))) return st;
   const size_t in_step = in_layout->point_step, out_step = out_layout->point_step;
   const bool in_host = on_device == 0, out_host = out_on_device == 0;
   size_t total = 0;
@@ -93,17 +74,12 @@ int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, c
   for (int i = 0; i < num_submaps; i++) {
     const lsr_submap& s = submaps[i];
     if (s.n_points == 0) continue;
-    if (!s.cloud) { set_last_error("submap with points and a null cloud"); return LSR_ERR_INVALID_ARGUMENT; }
-    if ((uintptr_t)s.cloud & 3) { set_last_error("submap cloud is not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
+    if ((st = arg_error(check_records(s.cloud, s.n_points, MAP_RECORD_LIMIT, true, "submaps[].cloud")))) return st;
     if ((uintptr_t)s.cloud & 15) aligned16 = false;
-    if (s.n_points > (size_t)INT32_MAX || (total += s.n_points) > (size_t)INT32_MAX) {
-      set_last_error("the map holds more than INT32_MAX records");
-      return LSR_ERR_INDEX_OVERFLOW;
-    }
+    if ((st = arg_error(check_record_count(total += s.n_points, MAP_RECORD_LIMIT, "submaps[] (the whole map)")))) return st;
   }
   if (total > capacity_points) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (total > 0 && !out_data) { set_last_error("null output buffer"); return LSR_ERR_INVALID_ARGUMENT; }
-  if ((uintptr_t)out_data & 3) { set_last_error("output buffer is not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
+  if ((st = arg_error(check_records(out_data, total, MAP_RECORD_LIMIT, true, "out_data")))) return st;
   if (in_host == out_host)
     for (int i = 0; i < num_submaps; i++)
       if (ranges_overlap(out_data, total * out_step, submaps[i].cloud, submaps[i].n_points * in_step)) {
@@ -155,11 +131,9 @@ int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, c
       const size_t take = std::min(left, piece_cap - piece);
       const unsigned char* src = static_cast<const unsigned char*>(submaps[i].cloud) + at * in_step;
       MapSlot S;
-      S.records = src;
-      if (in_host) {
-        S.records = h->staging.p + piece * in_step;
-        LSR_HIP(hipMemcpyAsync(h->staging.p + piece * in_step, src, take * in_step, hipMemcpyHostToDevice, h->stream));
-      }
+      const void* d_src = nullptr;
+      if ((st = stage_in_at(h, src, take * in_step, !in_host, h->stream, piece * in_step, &d_src))) return st;
+      S.records = static_cast<const unsigned char*>(d_src);
       S.first_out = (long long)((out_host ? 0 : done) + piece);
       S.count = (int)take;
       S.first_slice = n_slices;
@@ -208,12 +182,8 @@ int lsr_format_pcd_ascii(lsr_handle h, const void* data, size_t n_points, const 
     return st;
   // whatever was enqueued has finished before the call returns: the staging buffer and the caller's buffers are free again
   StreamDrain drain{h->stream};
-  const void* d = data;
-  if (!on_device) {
-    if ((st = h->staging.reserve(n_points * F.step))) return st;
-    LSR_HIP(hipMemcpyAsync(h->staging.p, data, n_points * F.step, hipMemcpyHostToDevice, h->stream));
-    d = h->staging.p;
-  }
+  const void* d = nullptr;
+  if ((st = stage_in(h, data, n_points * F.step, on_device != 0, h->stream, &d))) return st;
   hipEvent_t* ev = S.ev[0];
   if (h->profile) LSR_HIP(hipEventRecord(ev[PcdState::EV_L0], h->stream));
   if ((st = pcd_text_lengths(d, n_points, F, S.block_sums[0].p, S.offsets[0].p, h->stream))) return st;
@@ -225,7 +195,7 @@ int lsr_format_pcd_ascii(lsr_handle h, const void* data, size_t n_points, const 
   const size_t header_bytes = (size_t)pcd_header_text(n_points, F.n_fields == 4, header);
   const size_t size = header_bytes + body;
   double ms = 0.0;
-  if (h->profile && (st = pcd_add_ms(ev[PcdState::EV_L0], ev[PcdState::EV_L1], &ms))) return st;
+  if (h->profile && (st = add_ms(ev[PcdState::EV_L0], ev[PcdState::EV_L1], &ms))) return st;
   if (!out_text) {
     S.format_ms = ms;
     *n_bytes = size;
@@ -248,7 +218,7 @@ int lsr_format_pcd_ascii(lsr_handle h, const void* data, size_t n_points, const 
     LSR_HIP(hipMemcpyAsync(static_cast<unsigned char*>(out_text) + header_bytes, S.text.p, body, hipMemcpyDeviceToHost, h->stream));
   LSR_HIP(hipStreamSynchronize(h->stream));
   if (!out_on_device) std::memcpy(out_text, header, header_bytes);
-  if (h->profile && (st = pcd_add_ms(ev[PcdState::EV_W0], ev[PcdState::EV_W1], &ms))) return st;
+  if (h->profile && (st = add_ms(ev[PcdState::EV_W0], ev[PcdState::EV_W1], &ms))) return st;
   S.format_ms = ms;
   *n_bytes = size;
   return LSR_OK;
@@ -292,16 +262,14 @@ int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t 
   auto enqueue_lengths = [&](size_t k) -> int {
     const int par = (int)(k & 1);
     const size_t first = k * P, cnt = std::min(P, n_points - first);
-    const unsigned char* src = static_cast<const unsigned char*>(data) + first * F.step;
-    if (in_host) {
-      unsigned char* stage = h->staging.p + (size_t)par * p_max * F.step;
-      LSR_HIP(hipMemcpyAsync(stage, src, cnt * F.step, hipMemcpyHostToDevice, h->stream));
-      src = stage;
-    }
+    const void* src = nullptr;   // host pieces alternate between the two halves of the staging buffer
+    int e = stage_in_at(h, static_cast<const unsigned char*>(data) + first * F.step, cnt * F.step, !in_host, h->stream,
+                        (size_t)par * p_max * F.step, &src);
+    if (e) return e;
     d_piece[par] = src;
     count[par] = cnt;
     if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_L0], h->stream));
-    int e = pcd_text_lengths(src, cnt, F, S.block_sums[par].p, S.offsets[par].p, h->stream);
+    e = pcd_text_lengths(src, cnt, F, S.block_sums[par].p, S.offsets[par].p, h->stream);
     if (e) return e;
     if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_L1], h->stream));
     LSR_HIP(hipMemcpyAsync(S.totals.p + par, S.offsets[par].p + pcd_blocks(cnt), sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -312,7 +280,7 @@ int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t 
     const int par = (int)(k & 1);
     LSR_HIP(hipEventSynchronize(S.ev[par][PcdState::EV_DONE]));
     if (h->profile) {
-      int e = pcd_add_ms(S.ev[par][PcdState::EV_W0], S.ev[par][PcdState::EV_W1], &ms);
+      int e = add_ms(S.ev[par][PcdState::EV_W0], S.ev[par][PcdState::EV_W1], &ms);
       if (e) return e;
     }
     if (std::fwrite(S.pin[par].p, 1, bytes[par], file.f) != bytes[par]) return pcd_io_error("short write to", path);
@@ -326,7 +294,7 @@ int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t 
     LSR_HIP(hipEventSynchronize(S.ev[par][PcdState::EV_LEN]));
     bytes[par] = (size_t)S.totals.p[par];
     if (bytes[par] > count[par] * PCD_MAX_LINE_BYTES) { set_last_error("a piece's text is longer than its bound"); return LSR_ERR_HIP; }
-    if (h->profile && (st = pcd_add_ms(S.ev[par][PcdState::EV_L0], S.ev[par][PcdState::EV_L1], &ms))) return st;
+    if (h->profile && (st = add_ms(S.ev[par][PcdState::EV_L0], S.ev[par][PcdState::EV_L1], &ms))) return st;
     if (k + 1 < n_pieces && (st = enqueue_lengths(k + 1))) return st;
     if (h->profile) LSR_HIP(hipEventRecord(S.ev[par][PcdState::EV_W0], h->stream));
     if ((st = pcd_text_write(d_piece[par], count[par], F, S.offsets[par].p, S.text.p, h->stream))) return st;
@@ -347,15 +315,14 @@ int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* sub
   LSR_CHECK_HANDLE(h);
   if (!path || !n_bytes || !submaps || num_submaps <= 0) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
   size_t total = 0;
-  for (int i = 0; i < num_submaps; i++)
-    if (submaps[i].n_points > (size_t)INT32_MAX || (total += submaps[i].n_points) > (size_t)INT32_MAX) {
-      set_last_error("the map holds more than INT32_MAX records");
-      return LSR_ERR_INDEX_OVERFLOW;
-    }
-  if (total == 0) { set_last_error("an empty map has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }
+  int st;
+  for (int i = 0; i < num_submaps; i++)   // (the size of the map buffer; lsr_assemble_map below checks the clouds themselves)
+    if ((st = arg_error(check_record_count(submaps[i].n_points, MAP_RECORD_LIMIT, "submaps[].n_points"))) ||
+        (st = arg_error(check_record_count(total += submaps[i].n_points, MAP_RECORD_LIMIT, "submaps[] (the whole map)"))))
+      return st;
+  if (total == 0) { set_last_error("submaps[]: an empty map has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }
   static const lsr_pc2_layout xyzi = {32, 0, 4, 8, 16};   // pcl::PointXYZI, what map_ptr holds
-  int st = h->pcd.map.reserve(total * xyzi.point_step);
-  if (st) return st;
+  if ((st = h->pcd.map.reserve(total * xyzi.point_step))) return st;
   size_t n = 0;
   if ((st = lsr_assemble_map(h, submaps, num_submaps, in_layout, on_device, poses16, h->pcd.map.p, total, &xyzi, 1, nullptr, &n))) return st;
   return lsr_save_pcd_ascii(h, path, h->pcd.map.p, n, &xyzi, 1, n_bytes);

@@ -40,17 +40,6 @@ struct PcdReadJob {
   std::vector<unsigned int> h_starts;
 };
 
-int check_out_layout(const lsr_pc2_layout* L) {
-  int st = check_layout(L);
-  if (st) return st;
-  const int64_t f[4] = {(int64_t)L->offset_x, (int64_t)L->offset_y, (int64_t)L->offset_z,
-                        L->offset_intensity >= 0 ? (int64_t)L->offset_intensity : (int64_t)-1};
-  for (int a = 0; a < 4; a++)
-    for (int b = a + 1; b < 4; b++)
-      if (f[a] >= 0 && f[a] == f[b]) { set_last_error("PointCloud2 layout: output fields overlap"); return LSR_ERR_INVALID_ARGUMENT; }
-  return LSR_OK;
-}
-
 int job_begin(PcdReadJob& J, lsr_handle h, const lsr_pc2_layout* out) {
   J.h = h;
   J.n_points = (size_t)J.H.info.n_points;
@@ -75,13 +64,6 @@ int job_begin(PcdReadJob& J, lsr_handle h, const lsr_pc2_layout* out) {
   S.h_status.p[0].pad = 0;
   LSR_HIP(hipMemcpyAsync(S.status.p, S.h_status.p, sizeof(PcdReadStatus), hipMemcpyHostToDevice, h->stream));
   LSR_HIP(hipStreamSynchronize(h->stream));   // h_status is written by the first piece's read-back
-  return LSR_OK;
-}
-
-int add_ms(hipEvent_t a, hipEvent_t b, double* ms) {
-  float t = 0.f;
-  LSR_HIP(hipEventElapsedTime(&t, a, b));
-  *ms += t;
   return LSR_OK;
 }
 
@@ -201,11 +183,10 @@ int job_end(PcdReadJob& J, void* out_records, int out_on_device, size_t* n_out) 
 int check_read_args(const void* out_records, size_t capacity_points, const lsr_pc2_layout* out_layout, const size_t* n_out) {
   if (!n_out) { set_last_error("bad argument"); return LSR_ERR_INVALID_ARGUMENT; }
   if (!out_records) return LSR_OK;
-  (void)capacity_points;
   int st = check_out_layout(out_layout);
   if (st) return st;
-  if ((uintptr_t)out_records & 3) { set_last_error("output buffer is not 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
-  return LSR_OK;
+  (void)capacity_points;   // a bound, not a count: the count is the file's, and load / decode hold it against the bound
+  return arg_error(check_records(out_records, 0, MAP_RECORD_LIMIT, true, "out_records"));
 }
 
 int refuse_kind(const PcdHeader& H) {

@@ -73,24 +73,14 @@ int lsr_transform_pc2(lsr_handle h, const void* data, size_t n_points, const lsr
   if (st) return st;
   SensorTf12 T;
   if ((st = lsr_sensor_transform_matrix(tf, T.m))) return st;
-  if (n_points == 0) return LSR_OK;
-  if (!data || !out_data) { set_last_error("null PointCloud2 data"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (n_points > (size_t)INT32_MAX / 2) { set_last_error("cloud too large"); return LSR_ERR_INVALID_ARGUMENT; }
-  if ((reinterpret_cast<size_t>(data) & 3) != 0 || (reinterpret_cast<size_t>(out_data) & 3) != 0) { set_last_error("PointCloud2 data must be 4-byte aligned"); return LSR_ERR_INVALID_ARGUMENT; }
-  const size_t bytes = n_points * (size_t)layout->point_step;
-  if (data != out_data) {   // equal or disjoint: the kernel copies records workgroup by workgroup
-    const uintptr_t a = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(out_data);
-    if (a < b + bytes && b < a + bytes) { set_last_error("data and out_data overlap: they must be equal (in place) or disjoint"); return LSR_ERR_INVALID_ARGUMENT; }
-  }
+  if (n_points == 0) return LSR_OK;   // nothing to move: the pointers are not looked at (lsr_deskew_pc2 differs: it still reports)
+  if ((st = arg_error(check_records_in_out(data, out_data, n_points, layout->point_step)))) return st;
   const int step = (int)layout->point_step, ox = (int)layout->offset_x, oy = (int)layout->offset_y, oz = (int)layout->offset_z;
-  if (on_device)   // returns when the records are complete, for a reader on any stream: a mailbox word, no copy, no synchronisation
-    return pc2_transform(data, out_data, step, ox, oy, oz, n_points, T, h->scratch, h->stream, true);
-  if ((st = h->staging.reserve(bytes))) return st;
-  LSR_HIP(hipMemcpyAsync(h->staging.p, data, bytes, hipMemcpyHostToDevice, h->stream));
-  if ((st = pc2_transform(h->staging.p, h->staging.p, step, ox, oy, oz, n_points, T, h->scratch, h->stream, false))) return st;
-  LSR_HIP(hipMemcpyAsync(out_data, h->staging.p, bytes, hipMemcpyDeviceToHost, h->stream));
-  LSR_HIP(hipStreamSynchronize(h->stream));
-  return LSR_OK;
+  // device records: returns when the records are complete, for a reader on any stream — a mailbox word, no copy, no synchronisation;
+  // host records: the copy down and its synchronisation are the wait
+  return records_in_records_out(h, data, out_data, n_points * (size_t)layout->point_step, on_device != 0, [&](const void* d_in, void* d_out) {
+    return pc2_transform(d_in, d_out, step, ox, oy, oz, n_points, T, h->scratch, h->stream, on_device != 0);
+  });
 }
 
 int lsr_odom_guess(const float* sim_trans16, const float* previous_odom16, const float* odom16, float* guess16) {

@@ -111,6 +111,26 @@ def _order_after_torch(reg, cloud):
         capi.check(reg._lib.lsr_wait_stream(reg._h, C.c_void_p(torch.cuda.current_stream(cloud.device).cuda_stream)), "lsr_wait_stream")
 
 
+def _payload_args(reg, data, point_step: int = 1):
+    """A record buffer `reg` is about to read — a raw PointCloud2 `data` buffer or records of `point_step` bytes; bytes / bytearray,
+    numpy array or CUDA tensor — -> (pointer, n_records, on_device, keepalive) through _record_args.  The keepalive is the buffer the
+    core reads: the uint8 view of the host array, or the tensor, behind which `reg`'s stream is ordered after torch's current one."""
+    host = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data
+    ptr, n, dev, keep = _record_args(host, point_step)
+    if dev:
+        _order_after_torch(reg, keep)
+    return C.c_void_p(ptr), n, dev, keep if dev else keep.view(np.uint8)
+
+
+def _payload_pair(reg, data, out):
+    """(data, out) of a records -> records method -> (source pointer, destination pointer, on_device, out).  out: None = a new buffer
+    of data's kind (uint8 numpy array / CUDA tensor), else the buffer to write (`data` itself: in place)."""
+    src, _, dev, keep = _payload_args(reg, data)
+    if out is None:
+        out = keep.new_empty(keep.shape) if dev else np.empty_like(keep)
+    return src, C.c_void_p(out.data_ptr() if dev else out.ctypes.data), dev, out
+
+
 class Registration:
     """pcl::Registration<PointXYZI, PointXYZI>-shaped base (SURVEY.md §8b)."""
 
@@ -271,12 +291,7 @@ class Registration:
         filter; None: the payload is in the robot frame already."""
         lay = self._layout(point_step, offsets)
         n_out = C.c_size_t()
-        if _is_torch_cuda(data):
-            _order_after_torch(self, data)
-            ptr, dev, keep = C.c_void_p(data.data_ptr()), 1, data
-        else:
-            keep = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
-            ptr, dev = C.c_void_p(keep.ctypes.data), 0
+        ptr, _, dev, keep = _payload_args(self, data)
         if sensor_transform is None:
             st = self._lib.lsr_set_input_source_pc2(self._h, ptr, int(n_points), C.byref(lay), float(scan_min_range), float(scan_max_range),
                                                     C.c_float(vg_size_for_input), dev, C.byref(n_out))
@@ -295,18 +310,7 @@ class Registration:
         HBM).  `out`: None = a new buffer, or the buffer to write (`data` itself: in place).  Returns the records."""
         lay = self._layout(point_step, offsets)
         tf = _sensor_transform(translation, rotation_xyzw)
-        if _is_torch_cuda(data):
-            import torch
-
-            if out is None:
-                out = torch.empty_like(data)
-            _order_after_torch(self, data)
-            src, dst, dev = C.c_void_p(data.data_ptr()), C.c_void_p(out.data_ptr()), 1
-        else:
-            keep = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
-            if out is None:
-                out = np.empty_like(keep)
-            src, dst, dev = C.c_void_p(keep.ctypes.data), C.c_void_p(out.ctypes.data), 0
+        src, dst, dev, out = _payload_pair(self, data, out)
         capi.check(self._lib.lsr_transform_pc2(self._h, src, int(n_points), C.byref(lay), C.byref(tf), dev, dst), "transformPointCloud2")
         return out
 
@@ -340,18 +344,7 @@ class Registration:
         lay = self._layout(point_step, offsets)
         info = capi.DeskewInfo()
         n_points = int(n_points)
-        if _is_torch_cuda(data):
-            import torch
-
-            if out is None:
-                out = torch.empty_like(data)
-            _order_after_torch(self, data)
-            src, dst, dev = C.c_void_p(data.data_ptr()), C.c_void_p(out.data_ptr()), 1
-        else:
-            keep = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
-            if out is None:
-                out = np.empty_like(keep)
-            src, dst, dev = C.c_void_p(keep.ctypes.data), C.c_void_p(out.ctypes.data), 0
+        src, dst, dev, out = _payload_pair(self, data, out)
         capi.check(self._lib.lsr_deskew_pc2(self._h, src, n_points, C.byref(lay), float(scan_time), dev, dst, C.byref(info)),
                    "deskewPointCloud2")
         self._n_deskew = n_points
@@ -401,10 +394,12 @@ class Registration:
                                    out_offsets=(0, 4, 8, 16)) -> np.ndarray:
         """pcl::VoxelGrid(leaf).filter on a PointCloud2 payload (host), all four fields averaged per leaf; -> (m, out_point_step) uint8."""
         li, lo = self._layout(point_step, offsets), self._layout(out_point_step, out_offsets)
-        src = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8)
+        src, _, dev, keep = _payload_args(self, data)
+        if dev:
+            raise ValueError("voxelGridFilterPointCloud2 takes a host payload")
         out = np.zeros((max(int(n_points), 1), out_point_step), np.uint8)
         n_out = C.c_size_t()
-        capi.check(self._lib.lsr_voxel_grid_filter_pc2(self._h, C.c_void_p(src.ctypes.data), int(n_points), C.byref(li), C.c_float(leaf),
+        capi.check(self._lib.lsr_voxel_grid_filter_pc2(self._h, src, int(n_points), C.byref(li), C.c_float(leaf),
                                                        C.c_void_p(out.ctypes.data), out.shape[0], C.byref(lo), C.byref(n_out)),
                    "voxelGridFilterPointCloud2")
         return out[: n_out.value].copy()
@@ -501,12 +496,10 @@ class Registration:
         tensor (-> uint8 CUDA tensor, nothing leaves HBM).  `out`: None = a new buffer, or a contiguous uint8 buffer to write; the
         result is the view of it that holds the text."""
         lay = self._layout(*layout)
-        ptr, n, dev, keep = _record_args(records, int(layout[0]))
-        if dev:
-            _order_after_torch(self, keep)
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
         size = C.c_size_t()
         if out is None:
-            capi.check(self._lib.lsr_format_pcd_ascii(self._h, C.c_void_p(ptr), n, C.byref(lay), 1 if dev else 0, None, 0, 0, C.byref(size)),
+            capi.check(self._lib.lsr_format_pcd_ascii(self._h, ptr, n, C.byref(lay), 1 if dev else 0, None, 0, 0, C.byref(size)),
                        "formatPCDASCII")
             if dev:
                 import torch
@@ -524,7 +517,7 @@ class Registration:
             if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
                 raise ValueError("out must be a writeable contiguous uint8 buffer")
             flat, optr, cap = out.reshape(-1), out.ctypes.data, out.nbytes
-        capi.check(self._lib.lsr_format_pcd_ascii(self._h, C.c_void_p(ptr), n, C.byref(lay), 1 if dev else 0, C.c_void_p(optr), cap,
+        capi.check(self._lib.lsr_format_pcd_ascii(self._h, ptr, n, C.byref(lay), 1 if dev else 0, C.c_void_p(optr), cap,
                                                   1 if out_dev else 0, C.byref(size)), "formatPCDASCII")
         return flat[: size.value]
 
@@ -532,11 +525,9 @@ class Registration:
         """pcl::io::savePCDFileASCII(path, cloud) through lsr_save_pcd_ascii: the same bytes, formatted on the device piece by piece
         while this thread writes the file.  `records` as for formatPCDASCII.  Returns the file's size in bytes."""
         lay = self._layout(*layout)
-        ptr, n, dev, keep = _record_args(records, int(layout[0]))
-        if dev:
-            _order_after_torch(self, keep)
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
         size = C.c_size_t()
-        capi.check(self._lib.lsr_save_pcd_ascii(self._h, os.fsencode(path), C.c_void_p(ptr), n, C.byref(lay), 1 if dev else 0, C.byref(size)),
+        capi.check(self._lib.lsr_save_pcd_ascii(self._h, os.fsencode(path), ptr, n, C.byref(lay), 1 if dev else 0, C.byref(size)),
                    "savePCDFileASCII")
         return int(size.value)
 
