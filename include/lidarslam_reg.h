@@ -39,7 +39,7 @@ typedef enum lsr_status {
   LSR_ERR_HIP = -3,             /* a HIP call failed; see lsr_last_error() */
   LSR_ERR_NO_TARGET = -4,       /* align/getFitnessScore before setInputTarget */
   LSR_ERR_NO_SOURCE = -5,       /* align/getFitnessScore before setInputSource */
-  LSR_ERR_NOT_IMPLEMENTED = -6, /* a .pcd file the readers do not take: DATA binary_compressed, coordinates that are not 4-byte floats
+  LSR_ERR_NOT_IMPLEMENTED = -6, /* a .pcd file the readers do not take: DATA binary_compressed (without LSR_PCD_READ_COMPRESSED), coordinates that are not 4-byte floats
                                    (lsr_parse_pcd_header, lsr_decode_pcd, lsr_load_pcd; until round 6 the NDT neighbourhood KDTREE too) */
   LSR_ERR_INDEX_OVERFLOW = -7,  /* voxel index space exceeds int32 (PCL: "Leaf size is too small") */
   LSR_ERR_TOO_FEW_POINTS = -8,  /* GICP: cloud smaller than k_correspondences */
@@ -83,6 +83,10 @@ typedef enum lsr_key {
                                          pass, scan, index pass, parse pass; copies outside the brackets) of the last lsr_decode_pcd /
                                          lsr_load_pcd / lsr_set_input_target_pcd of an ASCII file on this object, summed over its
                                          pieces; else 0 */
+  LSR_PCD_INFLATE_MS = 14,            /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the inflate launches (block
+                                         maps, scan, source words, doubling passes, record gather; copies outside the brackets) of the
+                                         last lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd of a DATA binary_compressed file
+                                         on this object; else 0 (0 after a file of another kind) */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -135,6 +139,10 @@ typedef enum lsr_key {
   LSR_PCD_UNRESOLVED_TOKENS = 53,     /* read-only (lsr_get_i32): how many values of the last lsr_decode_pcd / lsr_load_pcd /
                                          lsr_set_input_target_pcd on this object the device left to the C library's strtof (0 for every
                                          text whose values have at most 19 significant digits) */
+  LSR_PCD_READ_COMPRESSED = 54,       /* 1 = lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd on this object read DATA
+                                         binary_compressed files, the LZF stream inflated on the device; 0 (default) = they refuse such a
+                                         file with LSR_ERR_NOT_IMPLEMENTED.  Any other value is LSR_ERR_INVALID_ARGUMENT.  Per object, no
+                                         environment preset */
   LSR_GICP_SOLVER = 51                /* GICP inner optimiser (lsr_gicp_solver): LSR_GICP_GAUSS_NEWTON (default) or LSR_GICP_BFGS, the
                                          reference's own schedule (PCL's port of GSL vector_bfgs2: Fletcher line search, memoryless
                                          direction update, |g| < 1e-2 / max_inner_iterations / no progress).  Per object, no environment
@@ -586,7 +594,7 @@ int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* sub
                            int on_device, const double* poses16 /* nullable */, size_t* n_bytes);
 
 /* ---- reading .pcd files (the other half of map.pcd) ------------------------------------------ */
-/* PCD v0.7 files, DATA ascii and DATA binary, decoded on the device into records of an lsr_pc2_layout.  The semantics are RESTATED from
+/* PCD v0.7 files, DATA ascii, DATA binary and (with LSR_PCD_READ_COMPRESSED = 1) DATA binary_compressed, decoded on the device into records of an lsr_pc2_layout.  The semantics are RESTATED from
  * knowledge of the format and of the C library, and unpinned, like SURVEY.md 9.10 (the reference has no reader: "map save only").
  * Header (parsed on the host): lines ending in '\n'; `#` lines are comments; entries VERSION, FIELDS (or COLUMNS), SIZE, TYPE, COUNT
  * (default all 1), WIDTH, HEIGHT (default 1), VIEWPOINT (default 0 0 0 1 0 0 0; returned, never applied), POINTS (default WIDTH * HEIGHT)
@@ -601,13 +609,27 @@ int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* sub
  * rounding mode, by integer arithmetic on the device (values the device cannot decide, possible only beyond 19 significant digits, are
  * settled by strtof on the host: LSR_PCD_UNRESOLVED_TOKENS).  nan, +nan = 0x7fc00000, -nan = 0xffc00000.
  * Binary body: POINTS records of (sum of SIZE * COUNT) bytes from the byte behind the DATA line, the four fields copied bit for bit.
+ * Compressed body (read only with LSR_PCD_READ_COMPRESSED = 1; restated from knowledge of PCL and liblzf, unpinned): uint32 compressed_size,
+ * uint32 uncompressed_size, little endian, then compressed_size bytes of ONE LZF stream; bytes behind it are ignored.  The inflated image
+ * has uncompressed_size = POINTS * (sum of SIZE * COUNT) bytes and is field-major: per entry of FIELDS, in header order (`_` and skipped
+ * fields included), a block of POINTS * SIZE * COUNT bytes, point i at i * SIZE * COUNT inside it.  The stream is liblzf's: a control
+ * byte c < 32 copies the next c + 1 bytes; otherwise len = c >> 5 (len == 7: len += next byte), distance = ((c & 31) << 8 | next byte) + 1,
+ * and len + 2 bytes are copied from `distance` bytes back in the output, byte by byte (distance < len + 2 repeats a pattern).  It is
+ * inflated on the device (csrc/pcd_lzf.hip); the host reads the two size words and nothing else of the body.  Both sizes are at most
+ * 2^31 - 1.  The four fields' bytes are copied bit for bit, as from a binary body.
  * Output: records of out_layout (rules and refusals of lsr_assemble_map's output layout; offset_intensity < 0 drops the intensity), every
  * byte outside the fields zero.
  * Errors: LSR_ERR_INVALID_ARGUMENT — a required entry missing or malformed ("header incomplete" when the bytes end before the DATA
  * line), x, y or z absent, POINTS != WIDTH * HEIGHT, POINTS == 0; an ASCII line with fewer values than the fields demand, a value outside
  * the grammar, a line too long, fewer point lines than POINTS (lsr_last_error() names the file byte offset of the line's first byte; of
- * several bad lines the earliest); a binary body shorter than POINTS records; capacity_points below POINTS.  LSR_ERR_NOT_IMPLEMENTED —
- * DATA binary_compressed; x, y, z or intensity not a 4-byte float.  LSR_ERR_INDEX_OVERFLOW — more than INT32_MAX points. */
+ * several bad lines the earliest); a binary body shorter than POINTS records; capacity_points below POINTS.  A compressed body, in this
+ * order: shorter than the 8 bytes of its size words; (LSR_ERR_INDEX_OVERFLOW) a size above 2^31 - 1; uncompressed_size != POINTS * record
+ * bytes; compressed_size 0; compressed_size above the bytes that follow; capacity_points below POINTS; then, found on the device, a token
+ * that passes the end of the stream, a reference to before the first output byte, output past uncompressed_size (lsr_last_error() names
+ * the file byte offset of the token's control byte, "byte offset N"; of several bad tokens the earliest) and a stream that ends with
+ * fewer than uncompressed_size bytes put out (no offset).  LSR_ERR_NOT_IMPLEMENTED — DATA binary_compressed on an object without
+ * LSR_PCD_READ_COMPRESSED = 1 (the default); x, y, z or intensity not a 4-byte float (this one first).  LSR_ERR_INDEX_OVERFLOW — more than
+ * INT32_MAX points. */
 #define LSR_PCD_READ_MAX_LINE_BYTES 1024
 typedef struct lsr_pcd_info {
   uint64_t n_points, width, height, data_offset; /* data_offset: of the body's first byte */
@@ -627,7 +649,8 @@ int lsr_decode_pcd(lsr_handle h, const void* image, size_t n_bytes, int on_devic
                    const lsr_pc2_layout* out_layout, int out_on_device, size_t* n_out);
 /* The same from the file `path`, read in pieces of LSR_PCD_READ_PIECE_BYTES through two pinned buffers kept on the object: an ASCII piece
  * is cut at its last '\n' and what lies behind it is carried into the next; the calling thread reads piece k + 1 while piece k is parsed on
- * the object's stream; reading stops once POINTS lines are in.  The records do not depend on the piece size.  LSR_ERR_IO, with errno's
+ * the object's stream; reading stops once POINTS lines are in.  A compressed body is copied whole into HBM in such pieces (piece k + 1 read
+ * while piece k is copied; reading stops after 8 + compressed_size body bytes) and inflated once.  The records do not depend on the piece size.  LSR_ERR_IO, with errno's
  * text in lsr_last_error(), when the file cannot be opened or read. */
 int lsr_load_pcd(lsr_handle h, const char* path, void* out_records, size_t capacity_points, const lsr_pc2_layout* out_layout,
                  int out_on_device, size_t* n_out);

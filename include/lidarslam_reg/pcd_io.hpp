@@ -1,6 +1,7 @@
 // lidarslam_reg/pcd_io.hpp — header-only helpers over lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (lidarslam_reg.h): map.pcd written
 // from the device, the bytes pcl::io::savePCDFileASCII writes — and over lsr_load_pcd / lsr_set_input_target_pcd: such a file (or any
-// PCD v0.7 file, DATA ascii or binary, with float x y z [intensity]) read back on the device.
+// PCD v0.7 file, DATA ascii or binary — binary_compressed after pcdReadCompressed(h, true) —, with float x y z [intensity]) read back on
+// the device.
 //
 //   graph_based_slam/src/graph_based_slam_component.cpp:369   if (do_save_map) {pcl::io::savePCDFileASCII("map.pcd", *map_ptr);} // too heavy
 //
@@ -65,6 +66,18 @@ inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<
     std::memcpy(poses16.data() + 16 * i, M.data(), 16 * sizeof(double));
   }
   return saveMapPCD(h, path, submaps, poses16.data(), submaps_on_device);
+}
+
+// Whether lsr_load_pcd / lsr_set_input_target_pcd / lsr_decode_pcd of this object read DATA binary_compressed files (what
+// pcl::io::savePCDFileBinaryCompressed writes), the LZF stream inflated on the device (LSR_PCD_READ_COMPRESSED; off by default: such a
+// file is then refused as not implemented).
+inline bool pcdReadCompressed(lsr_handle h, bool on) {
+  const int st = lsr_set_i32(h, LSR_PCD_READ_COMPRESSED, on ? 1 : 0);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::pcdReadCompressed] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  return true;
 }
 
 // pcl::io::loadPCDFile(path, cloud) for the fields x y z [intensity]: the file's records, in `layout`, into `payload` (resized to

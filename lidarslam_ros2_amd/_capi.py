@@ -23,6 +23,7 @@ KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
  POSE_GRAPH_COMBINE_MS) = range(12)
 PCD_FORMAT_MS, PCD_PIECE_RECORDS = 12, 50
 PCD_PARSE_MS, PCD_READ_PIECE_BYTES, PCD_UNRESOLVED_TOKENS = 13, 52, 53
+PCD_INFLATE_MS, PCD_READ_COMPRESSED = 14, 54
 PCD_READ_MAX_LINE_BYTES = 1024
 ERR_NOT_IMPLEMENTED, ERR_INDEX_OVERFLOW = -6, -7
 ERR_IO = -9

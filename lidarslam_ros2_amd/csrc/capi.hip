@@ -165,6 +165,7 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_POSE_GRAPH_COMBINE_MS: *v = h->pose_graph.stage_ms[2]; return LSR_OK;
     case LSR_PCD_FORMAT_MS: *v = h->pcd.format_ms; return LSR_OK;
     case LSR_PCD_PARSE_MS: *v = h->pcd_read.parse_ms; return LSR_OK;
+    case LSR_PCD_INFLATE_MS: *v = h->pcd_read.inflate_ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -220,6 +221,9 @@ int lsr_set_i32(lsr_handle h, int key, int v) {
     case LSR_PCD_READ_PIECE_BYTES:
       if (v < PCDR_PIECE_MIN || v > PCDR_PIECE_MAX) { set_last_error("PCD read piece size must be in 2048 .. 1 << 28 bytes"); return LSR_ERR_INVALID_ARGUMENT; }
       h->pcd_read.piece_bytes = v; return LSR_OK;
+    case LSR_PCD_READ_COMPRESSED:
+      if (v != 0 && v != 1) { set_last_error("LSR_PCD_READ_COMPRESSED must be 0 or 1"); return LSR_ERR_INVALID_ARGUMENT; }
+      h->pcd_read.read_compressed = v; return LSR_OK;
     default: set_last_error("unknown i32 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -247,6 +251,7 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_MAP_ASSEMBLY_FORM: *v = h->map_form; return LSR_OK;
     case LSR_PCD_PIECE_RECORDS: *v = h->pcd.piece_records; return LSR_OK;
     case LSR_PCD_READ_PIECE_BYTES: *v = h->pcd_read.piece_bytes; return LSR_OK;
+    case LSR_PCD_READ_COMPRESSED: *v = h->pcd_read.read_compressed; return LSR_OK;
     case LSR_PCD_UNRESOLVED_TOKENS: *v = h->pcd_read.unresolved; return LSR_OK;
     case LSR_TARGET_PREPARED:
       if (h->method == LSR_METHOD_GICP) *v = gicp_target_prepared(h) ? 1 : 0;

@@ -1,6 +1,7 @@
 // Reading .pcd files: lsr_parse_pcd_header, lsr_decode_pcd, lsr_load_pcd and lsr_set_input_target_pcd of the C ABI
-// (include/lidarslam_reg.h).  Host-side orchestration only: the header, the pieces, the launches of pcd_read, the file, and the C
-// library's strtof for the tokens the device left unresolved.
+// (include/lidarslam_reg.h).  Host-side orchestration only: the header, the pieces, the launches of pcd_read and pcd_lzf, the file, the
+// two size words of a compressed body (the host reads nothing else of it), and the C library's strtof for the tokens the device left
+// unresolved.
 #include <sys/types.h>
 
 #include <algorithm>
@@ -30,7 +31,7 @@ struct PcdReadJob {
   PcdAsciiPlan ap;
   PcdBinaryPlan bp;
   size_t n_points = 0, step = 0, done = 0;
-  double ms = 0.0;
+  double ms = 0.0, inflate_ms = 0.0;
   unsigned int unresolved_seen = 0;
   // the piece in flight
   size_t keep = 0, text_bytes = 0;
@@ -175,6 +176,7 @@ int job_end(PcdReadJob& J, void* out_records, int out_on_device, size_t* n_out) 
   LSR_HIP(hipMemcpyAsync(out_records, S.records.p, J.n_points * J.step, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
   LSR_HIP(hipStreamSynchronize(h->stream));
   S.parse_ms = J.ms;
+  S.inflate_ms = J.inflate_ms;
   S.unresolved = (int)std::min<unsigned int>(J.unresolved_seen, (unsigned int)INT32_MAX);
   *n_out = J.n_points;
   return LSR_OK;
@@ -189,9 +191,34 @@ int check_read_args(const void* out_records, size_t capacity_points, const lsr_p
   return arg_error(check_records(out_records, 0, MAP_RECORD_LIMIT, true, "out_records"));
 }
 
-int refuse_kind(const PcdHeader& H) {
-  if (H.info.data_kind == 2) { set_last_error("PCD header: DATA binary_compressed is not read"); return LSR_ERR_NOT_IMPLEMENTED; }
+// DATA binary_compressed: the two size words at the head of the body (words: its first 8 bytes, read only when the body has them)
+// held against the header and against the body_bytes that lie behind the DATA line
+int compressed_sizes(const PcdHeader& H, const unsigned char* words, unsigned long long body_bytes, size_t* n_stream, size_t* n_out) {
+  if (body_bytes < 8) { set_last_error("PCD body: shorter than the two size words of DATA binary_compressed"); return LSR_ERR_INVALID_ARGUMENT; }
+  uint64_t c = 0, u = 0;
+  for (int i = 0; i < 4; i++) { c |= (uint64_t)words[i] << (8 * i); u |= (uint64_t)words[4 + i] << (8 * i); }
+  if (c > (uint64_t)INT32_MAX || u > (uint64_t)INT32_MAX) {
+    set_last_error("PCD body: compressed_size or uncompressed_size above 2^31 - 1");
+    return LSR_ERR_INDEX_OVERFLOW;
+  }
+  const uint64_t image = H.info.n_points * (uint64_t)H.info.point_step;
+  if (u != image) {
+    set_last_error("PCD body: uncompressed_size " + std::to_string(u) + " where POINTS x record bytes is " + std::to_string(image));
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  if (c == 0) { set_last_error("PCD body: compressed_size is 0"); return LSR_ERR_INVALID_ARGUMENT; }
+  if (c > body_bytes - 8) {
+    set_last_error("PCD body: compressed_size " + std::to_string(c) + " where " + std::to_string(body_bytes - 8) + " bytes follow the size words");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  *n_stream = (size_t)c;
+  *n_out = (size_t)u;
   return LSR_OK;
+}
+
+int too_small() {
+  set_last_error("output buffer too small");
+  return LSR_ERR_INVALID_ARGUMENT;
 }
 
 // lsr_load_pcd; to_target: the records go to the object's own {32; 0,4,8,16} buffer (out_records and capacity are ignored)
@@ -216,13 +243,12 @@ int load_pcd(lsr_handle h, const char* path, void* out_records, size_t capacity_
       if (got < want - have && std::ferror(file.f)) return pcdr_io_error("cannot read", path);
       head.resize(have + got);
       bool incomplete = false;
-      st = pcd_parse_header(head.data(), head.size(), &J.H, &incomplete);
+      st = pcd_parse_header(head.data(), head.size(), &J.H, &incomplete, S.read_compressed != 0);
       if (!incomplete || got < want - have || want >= ((size_t)1 << 20)) break;
       want *= 4;
     }
     if (st) return st;
   }
-  if ((st = refuse_kind(J.H))) return st;
   const size_t n = (size_t)J.H.info.n_points;
   if (!out_records && !to_target) { *n_out = n; return LSR_OK; }
   if (to_target) {
@@ -231,12 +257,53 @@ int load_pcd(lsr_handle h, const char* path, void* out_records, size_t capacity_
     capacity_points = n;
     out_on_device = 1;
   }
-  if (capacity_points < n) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
-  if (fseeko(file.f, (off_t)J.H.info.data_offset, SEEK_SET) != 0) return pcdr_io_error("cannot seek in", path);
+  const bool compressed = J.H.info.data_kind == 2;
+  size_t n_stream = 0, n_image = 0;
+  if (compressed) {
+    // the size words are held against the file's length before anything else of the body is read
+    errno = 0;
+    if (fseeko(file.f, 0, SEEK_END) != 0) return pcdr_io_error("cannot seek in", path);
+    const off_t end = ftello(file.f);
+    if (end < 0) return pcdr_io_error("cannot seek in", path);
+    const unsigned long long body_bytes = (unsigned long long)end > J.H.info.data_offset ? (unsigned long long)end - J.H.info.data_offset : 0;
+    if (fseeko(file.f, (off_t)J.H.info.data_offset, SEEK_SET) != 0) return pcdr_io_error("cannot seek in", path);
+    unsigned char words[8] = {0};
+    if (body_bytes >= 8 && std::fread(words, 1, 8, file.f) != 8) return pcdr_io_error("cannot read", path);
+    if ((st = compressed_sizes(J.H, words, body_bytes, &n_stream, &n_image))) return st;
+  }
+  if (capacity_points < n) return too_small();
+  if (!compressed && fseeko(file.f, (off_t)J.H.info.data_offset, SEEK_SET) != 0) return pcdr_io_error("cannot seek in", path);
   if ((st = job_begin(J, h, out_layout))) return st;
   StreamDrain drain{h->stream};   // (destroyed before `file` and before J's host buffers: nothing is in flight when they go)
   const size_t P = (size_t)S.piece_bytes;
   unsigned long long file_off = J.H.info.data_offset;   // of the first byte of the buffer in hand
+
+  if (compressed) {
+    // the whole stream into HBM, piece k + 1 read while piece k is copied; then one inflate
+    const size_t piece = std::min(P, n_stream);
+    for (int par = 0; par < 2; par++)
+      if ((st = S.pin[par].reserve(piece))) return st;
+    if ((st = S.text.reserve(n_stream))) return st;
+    auto read_piece = [&](int par, size_t first) -> int {
+      const size_t cnt = std::min(piece, n_stream - first);
+      errno = 0;
+      if (std::fread(S.pin[par].p, 1, cnt, file.f) != cnt) return pcdr_io_error("cannot read", path);
+      return LSR_OK;
+    };
+    if ((st = read_piece(0, 0))) return st;
+    int par = 0;
+    for (size_t sent = 0; sent < n_stream; par ^= 1) {
+      const size_t cnt = std::min(piece, n_stream - sent);
+      LSR_HIP(hipMemcpyAsync(S.text.p + sent, S.pin[par].p, cnt, hipMemcpyHostToDevice, h->stream));
+      if (sent + cnt < n_stream && (st = read_piece(par ^ 1, sent + cnt))) return st;
+      LSR_HIP(hipStreamSynchronize(h->stream));
+      sent += cnt;
+    }
+    if ((st = pcd_lzf_inflate(S, S.text.p, n_stream, n_image, n, J.bp, S.records.p, file_off + 8, h->profile ? &J.inflate_ms : nullptr, h->stream)))
+      return st;
+    J.done = n;
+    return job_end(J, out_records, out_on_device, n_out);
+  }
 
   if (J.H.info.data_kind == 1) {
     const size_t rb = J.bp.rec_bytes, per_piece = std::max<size_t>(1, P / rb);
@@ -348,30 +415,47 @@ int lsr_decode_pcd(lsr_handle h, const void* image, size_t n_bytes, int on_devic
       LSR_HIP(hipMemcpyAsync(head.data(), image, head.size(), hipMemcpyDeviceToHost, h->stream));
       LSR_HIP(hipStreamSynchronize(h->stream));
       bool incomplete = false;
-      st = pcd_parse_header(head.data(), head.size(), &J.H, &incomplete);
+      st = pcd_parse_header(head.data(), head.size(), &J.H, &incomplete, S.read_compressed != 0);
       if (!incomplete || head.size() == n_bytes) break;
     }
   } else {
-    st = pcd_parse_header(image, n_bytes, &J.H);
+    st = pcd_parse_header(image, n_bytes, &J.H, nullptr, S.read_compressed != 0);
   }
   if (st) return st;
-  if ((st = refuse_kind(J.H))) return st;
   const size_t n = (size_t)J.H.info.n_points, body_off = (size_t)J.H.info.data_offset, body = n_bytes - body_off;
   if (body >= ((size_t)1 << 32)) { set_last_error("a body of 2^32 bytes or more: read the file with lsr_load_pcd"); return LSR_ERR_INDEX_OVERFLOW; }
   if (!out_records) { *n_out = n; return LSR_OK; }
-  if (capacity_points < n) { set_last_error("output buffer too small"); return LSR_ERR_INVALID_ARGUMENT; }
+  const bool compressed = J.H.info.data_kind == 2;
+  size_t n_stream = 0, n_image = 0;
+  if (compressed) {
+    unsigned char words[8] = {0};
+    if (body >= 8) {
+      if (on_device) {
+        LSR_HIP(hipMemcpyAsync(words, static_cast<const unsigned char*>(image) + body_off, 8, hipMemcpyDeviceToHost, h->stream));
+        LSR_HIP(hipStreamSynchronize(h->stream));
+      } else {
+        std::memcpy(words, host_image + body_off, 8);
+      }
+    }
+    if ((st = compressed_sizes(J.H, words, body, &n_stream, &n_image))) return st;
+  }
+  if (capacity_points < n) return too_small();
   if (J.H.info.data_kind == 1 && body < n * (size_t)J.H.info.point_step) { set_last_error("PCD body: shorter than POINTS records"); return LSR_ERR_INVALID_ARGUMENT; }
   if (J.H.info.data_kind == 0 && body == 0) { J.n_points = n; return too_few_lines(J, n_bytes); }
   if ((st = job_begin(J, h, out_layout))) return st;
   StreamDrain drain{h->stream};
   const unsigned char* d_body = static_cast<const unsigned char*>(image) + body_off;
-  const size_t used = J.H.info.data_kind == 1 ? n * (size_t)J.H.info.point_step : body;
+  const size_t used = compressed ? 8 + n_stream : (J.H.info.data_kind == 1 ? n * (size_t)J.H.info.point_step : body);
   if (!on_device) {
     if ((st = S.text.reserve(used))) return st;
     LSR_HIP(hipMemcpyAsync(S.text.p, host_image + body_off, used, hipMemcpyHostToDevice, h->stream));
     d_body = S.text.p;
   }
-  if (J.H.info.data_kind == 1) {
+  if (compressed) {
+    if ((st = pcd_lzf_inflate(S, d_body + 8, n_stream, n_image, n, J.bp, S.records.p, body_off + 8, h->profile ? &J.inflate_ms : nullptr, h->stream)))
+      return st;
+    J.done = n;
+  } else if (J.H.info.data_kind == 1) {
     if ((st = pcd_read_binary(d_body, n, J.bp, S.records.p, h->stream))) return st;
     J.done = n;
   } else {

@@ -111,28 +111,6 @@ __global__ __launch_bounds__(PCDR_WG) void pcdr_index_kernel(const unsigned char
   });
 }
 
-__device__ inline void pcdr_store_record(unsigned char* rec, const PcdOutFields& O, bool wide, const uint32_t* v) {
-  if (wide) {
-    uint4* q = reinterpret_cast<uint4*>(rec);
-    q[0] = make_uint4(v[0], v[1], v[2], 0u);
-    q[1] = make_uint4(v[3], 0u, 0u, 0u);
-    return;
-  }
-  uint32_t* w = reinterpret_cast<uint32_t*>(rec);   // records and offsets are 4-byte aligned (checked by the entry points)
-  const int nw = O.step >> 2;
-  for (int j = 0; j < nw; j++) {
-    uint32_t x = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (O.off[k] == 4 * j) x = v[k];
-    w[j] = x;
-  }
-}
-
-__device__ inline bool pcdr_is_wide(const PcdOutFields& O, const unsigned char* records) {
-  return O.step == 32 && O.off[0] == 0 && O.off[1] == 4 && O.off[2] == 8 && O.off[3] == 16 && ((uintptr_t)records & 15u) == 0;
-}
-
 __global__ __launch_bounds__(PCDR_WG) void pcdr_parse_kernel(const unsigned char* __restrict__ text, size_t n,
                                                              const unsigned int* __restrict__ line_start, unsigned long long n_lines,
                                                              PcdAsciiPlan P, unsigned char* __restrict__ records,
@@ -214,7 +192,7 @@ bool header_u64(const std::string& w, uint64_t* v) {
 
 }  // namespace
 
-int pcd_parse_header(const void* bytes, size_t n_bytes, PcdHeader* H, bool* incomplete) {
+int pcd_parse_header(const void* bytes, size_t n_bytes, PcdHeader* H, bool* incomplete, bool take_compressed) {
   if (incomplete) *incomplete = false;
   const char* text = static_cast<const char*>(bytes);
   std::vector<std::string> names, types;
@@ -345,7 +323,7 @@ int pcd_parse_header(const void* bytes, size_t n_bytes, PcdHeader* H, bool* inco
       set_last_error(std::string("PCD header: field ") + wanted[k] + " is not a 4-byte float (SIZE 4, TYPE F)");
       return LSR_ERR_NOT_IMPLEMENTED;
     }
-  if (data_kind == 2) { set_last_error("PCD header: DATA binary_compressed is not read"); return LSR_ERR_NOT_IMPLEMENTED; }
+  if (data_kind == 2 && !take_compressed) { set_last_error("PCD header: DATA binary_compressed is not read"); return LSR_ERR_NOT_IMPLEMENTED; }
   return LSR_OK;
 }
 

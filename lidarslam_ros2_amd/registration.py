@@ -558,7 +558,8 @@ class Registration:
 
     # -- reading .pcd files ----------------------------------------------------------------------------
     def decodePCD(self, image, layout=PC2_XYZI):
-        """The records of a whole .pcd file image (PCD v0.7, DATA ascii or binary; the inverse of formatPCDASCII), decoded on the device
+        """The records of a whole .pcd file image (PCD v0.7, DATA ascii or binary, binary_compressed after pcdReadCompressed(True); the
+        inverse of formatPCDASCII), decoded on the device
         through lsr_decode_pcd.  `image`: bytes / uint8 numpy array (-> (n, point_step) uint8 numpy array) or CUDA uint8 tensor (-> CUDA
         tensor, nothing leaves HBM).  `layout`: (point_step, (x, y, z, intensity or None)) of the records wanted."""
         lay = self._layout(*layout)
@@ -620,6 +621,14 @@ class Registration:
         if nbytes is not None:
             capi.check(self._lib.lsr_set_i32(self._h, capi.PCD_READ_PIECE_BYTES, int(nbytes)), "pcdReadPieceBytes")
         return self._geti(capi.PCD_READ_PIECE_BYTES)
+
+    def pcdReadCompressed(self, on: Optional[bool] = None) -> bool:
+        """Whether decodePCD / loadPCDFile / setInputTargetPCD of this object read DATA binary_compressed files, the LZF stream inflated
+        on the device (LSR_PCD_READ_COMPRESSED, off by default: such a file is then refused as not implemented): sets it when given,
+        returns the current value."""
+        if on is not None:
+            capi.check(self._lib.lsr_set_i32(self._h, capi.PCD_READ_COMPRESSED, 1 if on else 0), "pcdReadCompressed")
+        return bool(self._geti(capi.PCD_READ_COMPRESSED))
 
     def pcdUnresolvedTokens(self) -> int:
         """Values of the last decodePCD / loadPCDFile / setInputTargetPCD the device left to the C library (LSR_PCD_UNRESOLVED_TOKENS)."""
