@@ -87,6 +87,10 @@ typedef enum lsr_key {
                                          maps, scan, source words, doubling passes, record gather; copies outside the brackets) of the
                                          last lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd of a DATA binary_compressed file
                                          on this object; else 0 (0 after a file of another kind) */
+  LSR_PCD_DEFLATE_MS = 15,            /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the deflate launches
+                                         (field-major gather, chunk compressor, scan, and the compaction where the stream is written;
+                                         copies outside the brackets) of the last lsr_format_pcd / lsr_save_pcd / lsr_save_map_pcd with
+                                         LSR_PCD_BINARY_COMPRESSED on this object; else 0 (0 after a call of these with another kind) */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -133,7 +137,8 @@ typedef enum lsr_key {
                                          and two 16-byte stores per record), 2 = general (any layout).  The bytes are the same */
   LSR_PCD_PIECE_RECORDS = 50,         /* records per piece of lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (64 .. 1 << 22, default 1 << 20): a
                                          piece is formatted and copied while the calling thread writes the one before it.  The file's
-                                         bytes do not depend on it */
+                                         bytes do not depend on it.  lsr_save_pcd / lsr_save_map_pcd: the same for a binary body; a
+                                         compressed stream is copied and written in pieces of as many bytes as that many packed records */
   LSR_PCD_READ_PIECE_BYTES = 52,      /* bytes per piece of lsr_load_pcd / lsr_set_input_target_pcd (2048 .. 1 << 28, default 1 << 26): a piece
                                          is read from the file while the one before it is parsed.  The records do not depend on it */
   LSR_PCD_UNRESOLVED_TOKENS = 53,     /* read-only (lsr_get_i32): how many values of the last lsr_decode_pcd / lsr_load_pcd /
@@ -592,6 +597,51 @@ int lsr_save_pcd_ascii(lsr_handle h, const char* path, const void* data, size_t 
  * a map without any record is LSR_ERR_INVALID_ARGUMENT. */
 int lsr_save_map_pcd_ascii(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
                            int on_device, const double* poses16 /* nullable */, size_t* n_bytes);
+
+/* ---- map.pcd as DATA binary and DATA binary_compressed ---------------------------------------- */
+/* The same three entries with the body kind as an argument.  LSR_PCD_ASCII calls the entry above and gives its bytes; any value that is
+ * not one of the three is LSR_ERR_INVALID_ARGUMENT.  The formats (restated, unpinned, like SURVEY.md 9.10):
+ * Header: the text of the ASCII file — FIELDS x y z intensity, or x y z for a layout with offset_intensity < 0; SIZE 4, TYPE F, COUNT 1;
+ * width n, height 1, default viewpoint — with the last line "DATA binary\n" or "DATA binary_compressed\n".
+ * Binary body: n PACKED records of 12 or 16 bytes, the three or four fields copied bit for bit (NaN payloads, -0, denormals).  A stated
+ * deviation: pcl::io::savePCDFileBinary of a pcl::PointXYZI cloud writes the 32-byte struct, `_` padding fields with uninitialised bytes
+ * included; every PCD reader, PCL's too, loads the packed file into the same points, and it is half the size.
+ * Compressed body: uint32 compressed_size, uint32 uncompressed_size, little endian, then ONE LZF stream whose inflation is the
+ * field-major image — per field, in header order, a block of 4 n bytes — exactly what lsr_decode_pcd reads (above).  The stream is a
+ * PURE FUNCTION OF THE IMAGE (not of the piece size, of where input or output live, of the object or the call): the image is cut into
+ * chunks of LSR_PCD_LZF_CHUNK_BYTES (the last may be shorter), each compressed on its own — no reference reaches before its chunk's
+ * first byte, so the chunks' streams back to back are one valid stream —, a workgroup per chunk (csrc/pcd_deflate.hip).  Inside a chunk:
+ * the candidate of a position i with three bytes left in the chunk is the nearest earlier position of the chunk with the same three
+ * bytes (exact comparison); its length is the common extension, at most 264 and up to the chunk's end; the parse is greedy from the
+ * chunk's first byte (with a candidate a reference and on by its length, else a literal and on by one); literals go out in runs of at
+ * most 32, a run ends at a reference and at the chunk's end; a reference of length <= 8 has the two-byte form, from 9 the three-byte
+ * form.  uncompressed_size or a stream above 2^31 - 1 bytes is LSR_ERR_INDEX_OVERFLOW (the reader's own limit). */
+#define LSR_PCD_LZF_CHUNK_BYTES 4096
+typedef enum lsr_pcd_data { LSR_PCD_ASCII = 0, LSR_PCD_BINARY = 1, LSR_PCD_BINARY_COMPRESSED = 2 } lsr_pcd_data; /* = lsr_pcd_info.data_kind */
+/* lsr_format_pcd_ascii with a body kind: the whole file image into out_image (host, or HIP device buffer with out_on_device != 0; any
+ * alignment); out_image == NULL: only *n_bytes is set.  Same argument checks and refusals; no error touches out_image or *n_bytes.  A
+ * compressed image is compressed in HBM whole: the field-major image, the chunks' streams and the stream are kept on the object. */
+int lsr_format_pcd(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* layout, int on_device, int data_kind,
+                   void* out_image, size_t capacity_bytes, int out_on_device, size_t* n_bytes);
+/* lsr_save_pcd_ascii with a body kind: the same image written to `path`, without seeking.  Binary: in pieces of LSR_PCD_PIECE_RECORDS
+ * records through the object's two pinned buffers, piece k + 1 packed and copied while the calling thread writes piece k; no size limit
+ * but INT32_MAX records.  Compressed: the size words precede the stream, so the whole cloud is compressed in HBM first, the total read
+ * back, header and size words written, and the stream copied and written in pieces through the same two buffers.  Errors as for
+ * lsr_save_pcd_ascii: a file that fails after it was opened is closed and removed. */
+int lsr_save_pcd(lsr_handle h, const char* path, const void* data, size_t n_points, const lsr_pc2_layout* layout, int on_device, int data_kind,
+                 size_t* n_bytes);
+/* lsr_save_map_pcd_ascii with a body kind: lsr_assemble_map into the object's XYZI buffer, then lsr_save_pcd from it; byte-equal to
+ * those two calls. */
+int lsr_save_map_pcd(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
+                     int on_device, const double* poses16 /* nullable */, int data_kind, size_t* n_bytes);
+/* The compressor alone: the LZF stream, under the rule above, of the n_image bytes (1 .. 2^31 - 1; any alignment; host, or HIP device
+ * pointer with on_device != 0) at `image`, into out_stream (host, or HIP device buffer with out_on_device != 0) of capacity_bytes;
+ * *n_bytes = the stream's length, at most the sum over the chunks of c + ceil(c / 32).  out_stream == NULL: only *n_bytes is set.  What a
+ * compressed lsr_format_pcd puts behind its size words is this stream of the field-major image.  LSR_ERR_INVALID_ARGUMENT: null handle,
+ * image or n_bytes; n_image == 0; capacity_bytes below the length.  LSR_ERR_INDEX_OVERFLOW: n_image above 2^31 - 1.  No error touches
+ * out_stream or *n_bytes.  LSR_PCD_DEFLATE_MS covers it (without a gather). */
+int lsr_lzf_deflate(lsr_handle h, const void* image, size_t n_image, int on_device, void* out_stream, size_t capacity_bytes,
+                    int out_on_device, size_t* n_bytes);
 
 /* ---- reading .pcd files (the other half of map.pcd) ------------------------------------------ */
 /* PCD v0.7 files, DATA ascii, DATA binary and (with LSR_PCD_READ_COMPRESSED = 1) DATA binary_compressed, decoded on the device into records of an lsr_pc2_layout.  The semantics are RESTATED from

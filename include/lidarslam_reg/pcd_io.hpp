@@ -38,14 +38,45 @@ inline bool savePCDFileASCII(lsr_handle h, const std::string& path, const void* 
   return true;
 }
 
+// pcl::io::savePCDFileBinary(path, cloud) for the fields x y z [intensity]: a DATA binary file of PACKED records of 12 or 16 bytes, the
+// fields bit for bit (PCL writes the 32-byte PointXYZI struct with its padding; every PCD reader loads both into the same points).
+inline bool savePCDFileBinary(lsr_handle h, const std::string& path, const void* payload, size_t n,
+                              const lsr_pc2_layout& layout = pcdPointXYZILayout(), bool payload_on_device = false, size_t* n_bytes = nullptr) {
+  size_t bytes = 0;
+  const int st = lsr_save_pcd(h, path.c_str(), payload, n, &layout, payload_on_device ? 1 : 0, LSR_PCD_BINARY, &bytes);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::savePCDFileBinary] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_bytes) *n_bytes = bytes;
+  return true;
+}
+
+// pcl::io::savePCDFileBinaryCompressed(path, cloud) for the same fields: the field-major image as one LZF stream, compressed on the
+// device (the stream is the project's own parse, a valid LZF stream every PCD reader inflates to the same image).
+inline bool savePCDFileBinaryCompressed(lsr_handle h, const std::string& path, const void* payload, size_t n,
+                                        const lsr_pc2_layout& layout = pcdPointXYZILayout(), bool payload_on_device = false,
+                                        size_t* n_bytes = nullptr) {
+  size_t bytes = 0;
+  const int st = lsr_save_pcd(h, path.c_str(), payload, n, &layout, payload_on_device ? 1 : 0, LSR_PCD_BINARY_COMPRESSED, &bytes);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::savePCDFileBinaryCompressed] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_bytes) *n_bytes = bytes;
+  return true;
+}
+
 // The whole map of a MapArray as map.pcd in one call: every submap moved by its pose on the device — poses16_or_null: submaps.size()
 // column-major fp64 4x4 matrices, or nullptr = every submap's own position / orientation —, the map kept in HBM, its text formatted
 // there and written piece by piece.  The records are those lsr_assemble_map gives the same arguments.
+// data_kind: LSR_PCD_ASCII (the default: savePCDFileASCII's bytes), LSR_PCD_BINARY or LSR_PCD_BINARY_COMPRESSED.
 inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<lsr_submap>& submaps, const double* poses16_or_null,
-                       bool submaps_on_device = false, const lsr_pc2_layout& in_layout = pcdPointXYZILayout(), size_t* n_bytes = nullptr) {
+                       bool submaps_on_device = false, const lsr_pc2_layout& in_layout = pcdPointXYZILayout(), size_t* n_bytes = nullptr,
+                       int data_kind = LSR_PCD_ASCII) {
   size_t bytes = 0;
-  const int st = lsr_save_map_pcd_ascii(h, path.c_str(), submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0,
-                                        poses16_or_null, &bytes);
+  const int st = lsr_save_map_pcd(h, path.c_str(), submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0,
+                                  poses16_or_null, data_kind, &bytes);
   if (st != LSR_OK) {
     std::fprintf(stderr, "[lidarslam_reg::saveMapPCD] %s: %s\n", lsr_status_string(st), lsr_last_error());
     return false;
@@ -58,14 +89,15 @@ inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<
 // entries, or nullptr = the submaps' own poses.
 template <typename Pose>
 inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<lsr_submap>& submaps, const Pose* poses_or_null,
-                       bool submaps_on_device = false) {
-  if (!poses_or_null) return saveMapPCD(h, path, submaps, static_cast<const double*>(nullptr), submaps_on_device);
+                       bool submaps_on_device = false, int data_kind = LSR_PCD_ASCII) {
+  if (!poses_or_null)
+    return saveMapPCD(h, path, submaps, static_cast<const double*>(nullptr), submaps_on_device, pcdPointXYZILayout(), nullptr, data_kind);
   std::vector<double> poses16(16 * submaps.size());
   for (size_t i = 0; i < submaps.size(); i++) {
     const auto M = poses_or_null[i].matrix();
     std::memcpy(poses16.data() + 16 * i, M.data(), 16 * sizeof(double));
   }
-  return saveMapPCD(h, path, submaps, poses16.data(), submaps_on_device);
+  return saveMapPCD(h, path, submaps, poses16.data(), submaps_on_device, pcdPointXYZILayout(), nullptr, data_kind);
 }
 
 // Whether lsr_load_pcd / lsr_set_input_target_pcd / lsr_decode_pcd of this object read DATA binary_compressed files (what

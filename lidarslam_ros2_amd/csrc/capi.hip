@@ -166,6 +166,7 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_PCD_FORMAT_MS: *v = h->pcd.format_ms; return LSR_OK;
     case LSR_PCD_PARSE_MS: *v = h->pcd_read.parse_ms; return LSR_OK;
     case LSR_PCD_INFLATE_MS: *v = h->pcd_read.inflate_ms; return LSR_OK;
+    case LSR_PCD_DEFLATE_MS: *v = h->pcd_deflate.deflate_ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }

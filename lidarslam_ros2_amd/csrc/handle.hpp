@@ -5,6 +5,7 @@
 #include "gicp.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
+#include "pcd_deflate.hpp"
 #include "pcd_read.hpp"
 #include "pcd_text.hpp"
 #include "pose_graph.hpp"
@@ -97,7 +98,9 @@ struct lsr_handle_s {
 
   lsr::PcdState pcd;   // lsr_format_pcd_ascii / lsr_save_pcd_ascii / lsr_save_map_pcd_ascii (csrc/pcd_text.hip): buffers, kept between calls
 
-  lsr::PcdReadState pcd_read;   // lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd (csrc/pcd_read.hip): buffers, kept between calls
+  lsr::PcdDeflateState pcd_deflate;   // lsr_format_pcd / lsr_save_pcd / lsr_save_map_pcd (csrc/pcd_deflate.hip): image, slots, stream; kept between calls
+
+  lsr::PcdReadState pcd_read;  // lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd (csrc/pcd_read.hip): buffers, kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1): one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

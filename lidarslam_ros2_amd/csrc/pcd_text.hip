@@ -130,12 +130,12 @@ __global__ __launch_bounds__(PCD_WG) void pcd_write_kernel(const unsigned char* 
 
 }  // namespace
 
-int pcd_header_text(size_t n, bool with_intensity, char* out) {
+int pcd_header_text(size_t n, bool with_intensity, char* out, const char* data_word) {
   const int len = std::snprintf(out, PCD_MAX_HEADER_BYTES,
                                 "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z%s\nSIZE 4 4 4%s\nTYPE F F F%s\nCOUNT 1 1 1%s\n"
-                                "WIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA ascii\n",
+                                "WIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA %s\n",
                                 with_intensity ? " intensity" : "", with_intensity ? " 4" : "", with_intensity ? " F" : "",
-                                with_intensity ? " 1" : "", n, n);
+                                with_intensity ? " 1" : "", n, n, data_word);
   return len;
 }
 

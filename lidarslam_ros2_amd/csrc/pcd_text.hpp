@@ -49,8 +49,9 @@ struct PcdState {
   }
 };
 
-// the PCD header of a cloud of n records built by `+=` (width n, height 1, default viewpoint); returns its length (< PCD_MAX_HEADER_BYTES)
-int pcd_header_text(size_t n, bool with_intensity, char* out /* PCD_MAX_HEADER_BYTES */);
+// the PCD header of a cloud of n records built by `+=` (width n, height 1, default viewpoint), its last line "DATA <data_word>"; returns
+// its length (< PCD_MAX_HEADER_BYTES)
+int pcd_header_text(size_t n, bool with_intensity, char* out /* PCD_MAX_HEADER_BYTES */, const char* data_word = "ascii");
 
 inline size_t pcd_blocks(size_t n) { return (n + PCD_WG - 1) / PCD_WG; }
 

@@ -68,11 +68,14 @@ class MapArray:
         records[first_record[i]:first_record[i + 1]] is modified_map_array.submaps[i].cloud (:343-351).  -> (records, first_record)."""
         return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
 
-    def save_map(self, reg, path, poses=None) -> int:
+    def save_map(self, reg, path, poses=None, data="ascii") -> int:
         """`pcl::io::savePCDFileASCII("map.pcd", *map_ptr)` at the end of doPoseAdjustment (:369): the map by the stored poses, or by
         the optimiser's `poses` when given (4x4 fp64 each), written to `path` as ASCII PCD with fields x y z intensity — one call into
-        the registration object, the map never visits the host as records.  -> the file's size in bytes."""
-        return reg.saveMapPCDFileASCII(path, self.submaps, poses, self.layout)
+        the registration object, the map never visits the host as records.  `data`: "ascii" (the default: those bytes), "binary" or
+        "binary_compressed" (the LZF stream compressed on the device).  -> the file's size in bytes."""
+        if data == "ascii":
+            return reg.saveMapPCDFileASCII(path, self.submaps, poses, self.layout)
+        return reg.saveMapPCDFile(path, self.submaps, poses, self.layout, data)
 
     def stored_poses(self) -> np.ndarray:
         """(n, 4, 4) fp64: the pose every stored SubMap message stands for (Eigen::fromMsg, graph_based_slam_component.cpp:279-281)."""

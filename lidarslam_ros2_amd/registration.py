@@ -549,6 +549,104 @@ class Registration:
                    "saveMapPCDFileASCII")
         return int(size.value)
 
+    # -- map.pcd as DATA binary / DATA binary_compressed ----------------------------------------------
+    @staticmethod
+    def _pcd_kind(data) -> int:
+        """"ascii" / "binary" / "binary_compressed" -> lsr_pcd_data; an integer is passed on as it is (the library judges it)."""
+        if isinstance(data, str):
+            if data not in capi.PCD_DATA_KINDS:
+                raise ValueError(f"data must be one of {sorted(capi.PCD_DATA_KINDS)}")
+            return capi.PCD_DATA_KINDS[data]
+        return int(data)
+
+    def formatPCD(self, records, layout=PC2_XYZI, data="binary", out=None):
+        """The whole image of a .pcd file of these records through lsr_format_pcd: `data` = "binary" (packed records, the fields bit for
+        bit), "binary_compressed" (the field-major image as one LZF stream, compressed on the device; the stream depends on the
+        image alone) or "ascii" (formatPCDASCII's bytes).  `records`, `out` and the result as for formatPCDASCII."""
+        kind = self._pcd_kind(data)
+        lay = self._layout(*layout)
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
+        size = C.c_size_t()
+        if out is None:
+            capi.check(self._lib.lsr_format_pcd(self._h, ptr, n, C.byref(lay), 1 if dev else 0, kind, None, 0, 0, C.byref(size)), "formatPCD")
+            if dev:
+                import torch
+
+                out = torch.empty(size.value, dtype=torch.uint8, device=torch.device("cuda", self._device))
+            else:
+                out = np.zeros(size.value, np.uint8)
+        out_dev = _is_torch_cuda(out)
+        if out_dev:
+            if not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out must be a contiguous uint8 buffer")
+            flat, optr, cap = out.view(-1), out.data_ptr(), out.numel()
+            _order_after_torch(self, out)
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
+                raise ValueError("out must be a writeable contiguous uint8 buffer")
+            flat, optr, cap = out.reshape(-1), out.ctypes.data, out.nbytes
+        capi.check(self._lib.lsr_format_pcd(self._h, ptr, n, C.byref(lay), 1 if dev else 0, kind, C.c_void_p(optr), cap,
+                                            1 if out_dev else 0, C.byref(size)), "formatPCD")
+        return flat[: size.value]
+
+    def savePCDFile(self, path, records, layout=PC2_XYZI, data="ascii") -> int:
+        """The same image written to `path` through lsr_save_pcd: a binary body packed and copied piece by piece while this thread writes
+        the file; a compressed body compressed whole in HBM, then copied and written in pieces.  Returns the file's size in bytes."""
+        kind = self._pcd_kind(data)
+        lay = self._layout(*layout)
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
+        size = C.c_size_t()
+        capi.check(self._lib.lsr_save_pcd(self._h, os.fsencode(path), ptr, n, C.byref(lay), 1 if dev else 0, kind, C.byref(size)), "savePCDFile")
+        return int(size.value)
+
+    def saveMapPCDFile(self, path, submaps, poses=None, in_layout=PC2_XYZI, data="ascii") -> int:
+        """saveMapPCDFileASCII with a body kind (lsr_save_map_pcd): the submaps moved by their poses into a map that stays on the device,
+        and that map written as `data`.  Returns the file's size in bytes."""
+        kind = self._pcd_kind(data)
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("saveMapPCDFile needs at least one submap")
+        li = self._layout(*in_layout)
+        arr, keep, residency, _, P = self._submap_table(submaps, poses, int(in_layout[0]))
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        size = C.c_size_t()
+        capi.check(self._lib.lsr_save_map_pcd(self._h, os.fsencode(path), arr, n, C.byref(li), 1 if residency else 0,
+                                              P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, kind, C.byref(size)),
+                   "saveMapPCDFile")
+        return int(size.value)
+
+    def lzfDeflate(self, image):
+        """The compressor alone (lsr_lzf_deflate): the LZF stream of `image` — bytes / uint8 numpy array (-> uint8 numpy array) or CUDA
+        uint8 tensor (-> CUDA tensor) — under the chunked rule of include/lidarslam_reg.h; a function of the bytes alone."""
+        if _is_torch_cuda(image):
+            if not image.is_contiguous() or image.element_size() != 1:
+                raise ValueError("image must be a contiguous uint8 buffer")
+            _order_after_torch(self, image)
+            ptr, size, dev, keep = image.data_ptr(), image.numel(), 1, image
+        else:
+            keep = np.frombuffer(image, np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else np.ascontiguousarray(image).reshape(-1).view(np.uint8)
+            ptr, size, dev = keep.ctypes.data, keep.size, 0
+        n = C.c_size_t()
+        capi.check(self._lib.lsr_lzf_deflate(self._h, C.c_void_p(ptr), size, dev, None, 0, 0, C.byref(n)), "lzfDeflate")
+        if dev:
+            import torch
+
+            out = torch.empty(n.value, dtype=torch.uint8, device=torch.device("cuda", self._device))
+            _order_after_torch(self, out)
+            optr = out.data_ptr()
+        else:
+            out = np.zeros(n.value, np.uint8)
+            optr = out.ctypes.data
+        capi.check(self._lib.lsr_lzf_deflate(self._h, C.c_void_p(ptr), size, dev, C.c_void_p(optr), n.value, dev, C.byref(n)), "lzfDeflate")
+        return out
+
+    def pcdDeflateMs(self) -> float:
+        """With LSR_PROFILE = 1, the hipEvent time [ms] of the deflate launches of the last compressed formatPCD / savePCDFile /
+        saveMapPCDFile on this object (LSR_PCD_DEFLATE_MS); 0 after another kind."""
+        return self._getf(capi.PCD_DEFLATE_MS)
+
     def pcdPieceRecords(self, records: Optional[int] = None) -> int:
         """Records per piece of savePCDFileASCII / saveMapPCDFileASCII (LSR_PCD_PIECE_RECORDS, 64 .. 1 << 22): sets it when given,
         returns the current value.  The file's bytes do not depend on it."""
