@@ -832,6 +832,10 @@ int lsr_get_profile(lsr_handle h, lsr_profile* out, int reset);
 /* Host-only self check (needs no device): the angular coefficient tables of NDT eq. 6.19 / 6.21 at pose p6 by the scalar
  * formulas (jang_ref[24], hang_ref[48]) and by the 72-entry table the device evaluates one entry per lane (jang_tab, hang_tab). */
 int lsr_debug_angle_tables(const double* p6, int d1_sign, float* jang_ref, float* hang_ref, float* jang_tab, float* hang_tab);
+/* Host-only view of the guess decomposition (needs no device): p6 = the pose vector (x, y, z, roll, pitch, yaw) with which
+ * lsr_align starts from guess16 (column-major 4x4, nullable = identity) — the fp32 Euler angles of Eigen's eulerAngles(0,1,2),
+ * alias branch included (a rotation whose roll comes out positive is returned as (roll - pi, pi - pitch, yaw -+ pi), negated). */
+int lsr_debug_guess_pose(const float* guess16, double* p6);
 
 #ifdef __cplusplus
 }

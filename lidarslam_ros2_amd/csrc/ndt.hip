@@ -1666,6 +1666,15 @@ extern "C" int lsr_debug_angle_tables(const double* p6, int d1_sign, float* jang
   }
   return LSR_OK;
 }
+// Host-side view of the guess decomposition (no device needed): the pose vector p (translation, fp32 Euler XYZ angles of
+// Eigen's eulerAngles(0,1,2), widened) that ndt_fill_initial_state() stores at the entry of an align().
+extern "C" int lsr_debug_guess_pose(const float* guess16, double* p6) {
+  if (!p6) return LSR_ERR_INVALID_ARGUMENT;
+  lsr::NdtState st;
+  lsr::ndt_fill_initial_state(st, guess16, lsr::NdtParamsHost(), 0);
+  for (int i = 0; i < 6; i++) p6[i] = st.p[i];
+  return LSR_OK;
+}
 namespace lsr {
 
 // Start of a single align(): the initial controller state travels in the KERNEL ARGUMENTS (1 KiB) and one small launch

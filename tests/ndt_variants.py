@@ -6,6 +6,8 @@ a fourth entry: split = 1 — two waves per chunk in the 512-thread lane kernel.
 
 POSE_T_TOL = 1e-3   # metres   (north_star)
 POSE_R_TOL = 1e-4   # radians  (north_star)
+SCORE_TOL = 1e-5    # one derivative pass against the oracle: score, relative
+DERIV_TOL = 2e-5    # ... gradient and Hessian, relative to the largest entry of what is compared
 
 VARIANTS = [(1, 0, 2), (1, 0, 0), (1, 0, 1), (1, 64, 2), (0, 1024, 0), (0, 1024, 1), (0, 1024, 2), (0, 512, 0), (0, 512, 2),
             (0, 512, 0, 1), (0, 512, 1, 1), (0, 512, 2, 1)]

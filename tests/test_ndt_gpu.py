@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from ndt_variants import POSE_R_TOL, POSE_T_TOL, VARIANTS  # noqa: F401  (tolerances: north_star)
 from ndt_variants import tune as _tune
+from tilted_cases import assert_blocks   # score 1e-5, gradient and Hessian 2e-5, each block over its own largest entry
 
 
 @pytest.fixture(scope="module")
@@ -69,10 +70,7 @@ def test_derivative_pass_matches_oracle(O, case, res, hess):
         p = O.matrix_to_pose(case.guess) + np.r_[rng.uniform(-0.3, 0.3, 3), rng.uniform(-0.02, 0.02, 3)]
         s, g, H = ndt.derivatives(p, compute_hessian=hess)
         rs, rg, rH = O.ndt_derivatives(ref, case.source, p, compute_hessian=hess, resolution=res)
-        assert abs(s - rs) <= 1e-5 * abs(rs)
-        assert np.abs(g - rg).max() <= 2e-5 * np.abs(rg).max()
-        if hess:
-            assert np.abs(H - rH).max() <= 2e-5 * np.abs(rH).max()
+        assert_blocks((s, g, H), (rs, rg, rH), label=(res, hess, trial))
 
 
 @pytest.mark.parametrize("res,eps,max_iter", [(5.0, 0.01, None), (3.0, 0.01, None), (5.0, 1e-6, 30), (3.0, 1e-6, 30)])
@@ -213,9 +211,7 @@ def test_gpu_matches_the_committed_golden_fixture():
     assert np.array_equal(d["idx"], gold["leaf_idx"]) and np.array_equal(d["n"], gold["leaf_n"])
     # one derivative pass at the fixture's pose
     s, g, H = ndt.derivatives(gold["p"], compute_hessian=True)
-    assert abs(s - float(gold["score"])) <= 1e-5 * abs(float(gold["score"]))
-    assert np.abs(g - gold["grad"]).max() <= 2e-5 * np.abs(gold["grad"]).max()
-    assert np.abs(H - gold["hess"]).max() <= 2e-5 * np.abs(gold["hess"]).max()
+    assert_blocks((s, g, H), (float(gold["score"]), gold["grad"], gold["hess"]), label="golden DIRECT7")
     # align(): the reference's schedule and the tight one
     for eps, mi, key in ((0.01, 35, "eps001"), (1e-6, 30, "tight")):
         ndt.setTransformationEpsilon(eps)
@@ -236,9 +232,7 @@ def test_gpu_matches_the_committed_golden_fixture():
     in_tree = ~np.isnan(gold["leaf_centroid"][:, 0])
     assert np.array_equal(np.isnan(cen[:, 0]), ~in_tree) and np.array_equal(cen[in_tree], gold["leaf_centroid"][in_tree])
     s, g, H = ndt.derivatives(gold["p"], compute_hessian=True)
-    assert abs(s - float(gold["score_kdtree"])) <= 1e-5 * abs(float(gold["score_kdtree"]))
-    assert np.abs(g - gold["grad_kdtree"]).max() <= 2e-5 * np.abs(gold["grad_kdtree"]).max()
-    assert np.abs(H - gold["hess_kdtree"]).max() <= 2e-5 * np.abs(gold["hess_kdtree"]).max()
+    assert_blocks((s, g, H), (float(gold["score_kdtree"]), gold["grad_kdtree"], gold["hess_kdtree"]), label="golden KDTREE")
     ndt.setTransformationEpsilon(0.01)
     ndt.setMaximumIterations(35)
     ndt.align(gold["guess"])
@@ -264,10 +258,7 @@ def test_every_launch_variant_matches_the_oracle(O, case, variant):
         p = O.matrix_to_pose(case.guess) + np.r_[rng.uniform(-0.3, 0.3, 3), rng.uniform(-0.02, 0.02, 3)]
         s, g, H = ndt.derivatives(p, compute_hessian=hess)
         rs, rg, rH = O.ndt_derivatives(ref, case.source, p, compute_hessian=hess, resolution=res)
-        assert abs(s - rs) <= 1e-5 * abs(rs)
-        assert np.abs(g - rg).max() <= 2e-5 * np.abs(rg).max()
-        if hess:
-            assert np.abs(H - rH).max() <= 2e-5 * np.abs(rH).max()
+        assert_blocks((s, g, H), (rs, rg, rH), label=(variant, hess))
     for eps, max_iter in ((0.01, 35), (1e-6, 30)):
         ndt.setTransformationEpsilon(eps)
         ndt.setMaximumIterations(max_iter)
