@@ -91,6 +91,14 @@ typedef enum lsr_key {
                                          (field-major gather, chunk compressor, scan, and the compaction where the stream is written;
                                          copies outside the brackets) of the last lsr_format_pcd / lsr_save_pcd / lsr_save_map_pcd with
                                          LSR_PCD_BINARY_COMPRESSED on this object; else 0 (0 after a call of these with another kind) */
+  LSR_MAP_FILTER_BBOX_MS = 16,        /* read-only (lsr_get_f64), the next five likewise: with LSR_PROFILE = 1, the hipEvent time [ms] of
+                                         the launches of the last lsr_voxel_grid_filter_map / lsr_assemble_map_filtered /
+                                         lsr_save_map_pcd_filtered on this object (copies outside the brackets): the bounding-box pass; */
+  LSR_MAP_FILTER_KEY_MS = 17,         /* the key pass; */
+  LSR_MAP_FILTER_SORT_MS = 18,        /* the sort (both words and the two gathers of a wide index); */
+  LSR_MAP_FILTER_RUNS_MS = 19,        /* the run finder and its scan; */
+  LSR_MAP_FILTER_CENTROID_MS = 20,    /* the centroids; */
+  LSR_MAP_FILTER_WRITE_MS = 21,       /* the write of the output records.  Else 0 (the last two also after a call that only counted) */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -148,6 +156,9 @@ typedef enum lsr_key {
                                          binary_compressed files, the LZF stream inflated on the device; 0 (default) = they refuse such a
                                          file with LSR_ERR_NOT_IMPLEMENTED.  Any other value is LSR_ERR_INVALID_ARGUMENT.  Per object, no
                                          environment preset */
+  LSR_MAP_FILTER_KEY_BITS = 55,       /* read-only (lsr_get_i32): the bits of the largest leaf index of the last lsr_voxel_grid_filter_map /
+                                         lsr_assemble_map_filtered / lsr_save_map_pcd_filtered on this object (0 before the first, and
+                                         after a cloud without a finite point); above 32 the index was sorted as two words */
   LSR_GICP_SOLVER = 51                /* GICP inner optimiser (lsr_gicp_solver): LSR_GICP_GAUSS_NEWTON (default) or LSR_GICP_BFGS, the
                                          reference's own schedule (PCL's port of GSL vector_bfgs2: Fletcher line search, memoryless
                                          direction update, |g| < 1e-2 / max_inner_iterations / no progress).  Per object, no environment
@@ -642,6 +653,50 @@ int lsr_save_map_pcd(lsr_handle h, const char* path, const lsr_submap* submaps, 
  * out_stream or *n_bytes.  LSR_PCD_DEFLATE_MS covers it (without a gather). */
 int lsr_lzf_deflate(lsr_handle h, const void* image, size_t n_image, int on_device, void* out_stream, size_t capacity_bytes,
                     int out_on_device, size_t* n_bytes);
+
+/* ---- thinning the whole map: pcl::VoxelGrid with a 64-bit leaf index ------------------------- */
+/* What publishMap (scanmatcher_component.cpp:529-552) publishes and doPoseAdjustment (graph_based_slam_component.cpp:321-369) saves is the
+ * raw concatenation of the submaps: with a keyframe every metre or two and a sensor range of 100 m every spot is stored dozens of
+ * times.  These entries thin a map-sized cloud with a leaf size on the device, records in and records out.  pcl::VoxelGrid itself and
+ * lsr_voxel_grid_filter / _pc2 above carry the leaf index in int32 and refuse a cloud whose grid has more than INT32_MAX cells (a
+ * 500 m x 500 m x 40 m map at a 0.1 m leaf has 10^10); here the index has 64 bits.  The definition (csrc/map_filter.hip), otherwise
+ * that of lsr_voxel_grid_filter_pc2:
+ *   Bounding box: only records with finite x, y and z take part, the others are dropped.  inv_leaf = 1.0f / leaf; mn, mx = the
+ *   bounding box of the finite points.
+ *   Cells: min_b[k] = (int)floorf(mn[k] * inv_leaf), max_b[k] likewise, div_b[k] = max_b[k] - min_b[k] + 1; the cell of a point p is
+ *   c[k] = (int)(floorf(p[k] * inv_leaf) - (float)min_b[k]) — float arithmetic, one multiply, no FMA.
+ *   Leaf index: c0 + c1 * div_b0 + c2 * div_b0 * div_b1 in int64: wherever lsr_voxel_grid_filter_pc2 accepts the cloud, the number it uses.
+ *   Output: one record per occupied leaf, in ascending leaf index; x, y, z and intensity are each the float sum of the leaf's points
+ *   in ascending input index divided by (float) count.  An input layout without intensity yields intensity 0; an output layout
+ *   without intensity has no such field.  Every other byte of an output record is zero.
+ *   Limits, both LSR_ERR_INDEX_OVERFLOW: any |min_b[k]| or |max_b[k]| >= 2^24 (a float coordinate carries no leaf resolution there;
+ *   below it the float subtraction above is exact and equals PCL's integer one); any div_b[k] > 2^21 (so the index stays below
+ *   2^63).  Records: at most INT32_MAX / 2 in one call (what the sort orders), LSR_ERR_INDEX_OVERFLOW beyond.
+ *   Consequence: for every cloud lsr_voxel_grid_filter_pc2 accepts this filter returns the same bytes.  The output does not depend on
+ *   where the buffers live and is bit-identical from call to call.
+ * lsr_voxel_grid_filter_map: n_points records of in_layout at `data` (host, or HIP device pointer with on_device != 0) -> records of
+ * out_layout at out_data (host, or HIP device buffer with out_on_device != 0) of capacity_points records; *n_out = the number of occupied
+ * leaves.  out_data == NULL: only *n_out is set (capacity_points is ignored).  capacity_points below the count: LSR_ERR_INVALID_ARGUMENT
+ * with *n_out set to the count and out_data untouched.  A cloud without a finite point (n_points == 0 too) is LSR_OK with *n_out = 0.
+ * Layout, alignment and device-input ordering rules: those of lsr_assemble_map; LSR_ERR_INVALID_ARGUMENT also for a leaf that is not > 0
+ * (NaN included) and for an output range that overlaps the input records.  Every other error leaves all outputs untouched.  Two host
+ * waits per call: one for the bounding box, one for the leaf count, which sizes the output.  The scratch is kept on the object; a failed
+ * reservation is LSR_ERR_HIP.  What the object otherwise answers (target, source, final transformation, fitness) is unchanged.
+ * LSR_MAP_FILTER_KEY_BITS reports the index bits of the last call. */
+int lsr_voxel_grid_filter_map(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* in_layout, int on_device, float leaf,
+                              void* out_data, size_t capacity_points, const lsr_pc2_layout* out_layout, int out_on_device, size_t* n_out);
+/* lsr_assemble_map into a buffer of pcl::PointXYZI records kept on the object (the one lsr_save_map_pcd assembles into), followed by the
+ * filter from it: the bytes of those two calls made apart, the raw map never leaving HBM.  No first_record: a leaf mixes submaps.
+ * Arguments and errors: those of the two; out_data == NULL and a capacity below the count as above. */
+int lsr_assemble_map_filtered(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
+                              const double* poses16 /* nullable */, float leaf, void* out_data, size_t capacity_points,
+                              const lsr_pc2_layout* out_layout, int out_on_device, size_t* n_out);
+/* That, into a second buffer of pcl::PointXYZI records kept on the object, followed by lsr_save_pcd from it with data_kind: the file is
+ * byte-equal to the steps made apart.  *n_points (nullable) = the records in the file, *n_bytes = its size.  A map without a finite
+ * point is LSR_ERR_INVALID_ARGUMENT, like an empty one. */
+int lsr_save_map_pcd_filtered(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
+                              int on_device, const double* poses16 /* nullable */, float leaf, int data_kind,
+                              size_t* n_points /* nullable */, size_t* n_bytes);
 
 /* ---- reading .pcd files (the other half of map.pcd) ------------------------------------------ */
 /* PCD v0.7 files, DATA ascii, DATA binary and (with LSR_PCD_READ_COMPRESSED = 1) DATA binary_compressed, decoded on the device into records of an lsr_pc2_layout.  The semantics are RESTATED from

@@ -82,4 +82,81 @@ inline bool assembleMapDevice(lsr_handle h, const std::vector<lsr_submap>& subma
   return true;
 }
 
+// ---- the map thinned with a leaf size before it leaves the device (lsr_voxel_grid_filter_map, lsr_assemble_map_filtered) ----------
+// The forms with a leaf carry their own names: next to the bool and defaulted arguments above, an overload told apart by one float
+// argument would be chosen or refused by the literal's type (0.1 against 0.1f).
+
+// pcl::VoxelGrid(leaf).filter of n records of in_layout (host memory, or a HIP device pointer with records_on_device) into `payload`
+// (host): one record of out_layout per occupied leaf, in ascending leaf index, the leaf index carried in 64 bits — a map of
+// kilometres at a 0.1 m leaf.  Leaves payload empty on failure.
+inline bool voxelGridFilterMap(lsr_handle h, const void* records, size_t n, float leaf, std::vector<uint8_t>& payload,
+                               const lsr_pc2_layout& in_layout = pointXYZILayout(), const lsr_pc2_layout& out_layout = pointXYZILayout(),
+                               bool records_on_device = false) {
+  size_t m = 0;
+  int st = lsr_voxel_grid_filter_map(h, records, n, &in_layout, records_on_device ? 1 : 0, leaf, nullptr, 0, &out_layout, 0, &m);
+  if (st == LSR_OK) {
+    payload.assign(m * out_layout.point_step, 0);
+    if (m) st = lsr_voxel_grid_filter_map(h, records, n, &in_layout, records_on_device ? 1 : 0, leaf, payload.data(), m, &out_layout, 0, &m);
+  }
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::voxelGridFilterMap] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    payload.clear();
+    return false;
+  }
+  return true;
+}
+
+// assembleMap followed by that filter, the raw map never leaving HBM: payload receives the thinned map (host).  There is no
+// first_record: a leaf mixes submaps.  Two calls, like voxelGridFilterMap above: the count, which sizes the payload, then the records (a caller
+// that can spare the raw map's size on the device uses assembleMapFilteredDevice below: one call).
+inline bool assembleMapFiltered(lsr_handle h, const std::vector<lsr_submap>& submaps, const double* poses16_or_null, float leaf,
+                                std::vector<uint8_t>& payload, const lsr_pc2_layout& in_layout = pointXYZILayout(),
+                                const lsr_pc2_layout& out_layout = pointXYZILayout(), bool submaps_on_device = false) {
+  size_t m = 0;
+  int st = lsr_assemble_map_filtered(h, submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0, poses16_or_null, leaf,
+                                     nullptr, 0, &out_layout, 0, &m);
+  if (st == LSR_OK) {
+    payload.assign(m * out_layout.point_step, 0);
+    if (m)
+      st = lsr_assemble_map_filtered(h, submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0, poses16_or_null, leaf,
+                                     payload.data(), m, &out_layout, 0, &m);
+  }
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::assembleMapFiltered] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    payload.clear();
+    return false;
+  }
+  return true;
+}
+
+// The same with the optimiser's poses as objects (Pose::matrix().data() = 16 column-major doubles), or nullptr = the submaps' own.
+template <typename Pose>
+inline bool assembleMapFiltered(lsr_handle h, const std::vector<lsr_submap>& submaps, const Pose* poses_or_null, float leaf,
+                                std::vector<uint8_t>& payload) {
+  if (!poses_or_null) return assembleMapFiltered(h, submaps, static_cast<const double*>(nullptr), leaf, payload);
+  std::vector<double> poses16(16 * submaps.size());
+  for (size_t i = 0; i < submaps.size(); i++) {
+    const auto M = poses_or_null[i].matrix();
+    std::memcpy(poses16.data() + 16 * i, M.data(), 16 * sizeof(double));
+  }
+  return assembleMapFiltered(h, submaps, poses16.data(), leaf, payload);
+}
+
+// Device output: the thinned map stays in HBM (d_out: capacity_points records of out_layout; the raw map's record count always
+// suffices).  *n_out receives the record count.
+inline bool assembleMapFilteredDevice(lsr_handle h, const std::vector<lsr_submap>& submaps, const double* poses16_or_null, float leaf,
+                                      void* d_out, size_t capacity_points, size_t* n_out, bool submaps_on_device = true,
+                                      const lsr_pc2_layout& in_layout = pointXYZILayout(),
+                                      const lsr_pc2_layout& out_layout = pointXYZILayout()) {
+  size_t n = 0;
+  const int st = lsr_assemble_map_filtered(h, submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0, poses16_or_null,
+                                           leaf, d_out, capacity_points, &out_layout, /*out_on_device=*/1, &n);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::assembleMapFilteredDevice] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_out) *n_out = n;
+  return true;
+}
+
 }  // namespace lidarslam_reg

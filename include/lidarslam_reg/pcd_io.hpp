@@ -100,6 +100,38 @@ inline bool saveMapPCD(lsr_handle h, const std::string& path, const std::vector<
   return saveMapPCD(h, path, submaps, poses16.data(), submaps_on_device, pcdPointXYZILayout(), nullptr, data_kind);
 }
 
+// saveMapPCD with the map thinned first: pcl::VoxelGrid(leaf) over the whole map on the device, the leaf index carried in 64 bits
+// (lsr_save_map_pcd_filtered: assemble, filter, write; neither map visits the host as records).  n_points (nullable) receives the
+// number of records in the file.  (A name of its own: next to saveMapPCD's bool and defaulted arguments an overload told apart by one
+// float would be chosen or refused by the literal's type.)
+inline bool saveMapPCDFiltered(lsr_handle h, const std::string& path, const std::vector<lsr_submap>& submaps, const double* poses16_or_null,
+                               float leaf, int data_kind = LSR_PCD_ASCII, bool submaps_on_device = false,
+                               const lsr_pc2_layout& in_layout = pcdPointXYZILayout(), size_t* n_points = nullptr, size_t* n_bytes = nullptr) {
+  size_t bytes = 0, points = 0;
+  const int st = lsr_save_map_pcd_filtered(h, path.c_str(), submaps.data(), (int)submaps.size(), &in_layout, submaps_on_device ? 1 : 0,
+                                           poses16_or_null, leaf, data_kind, &points, &bytes);
+  if (st != LSR_OK) {
+    std::fprintf(stderr, "[lidarslam_reg::saveMapPCDFiltered] %s: %s\n", lsr_status_string(st), lsr_last_error());
+    return false;
+  }
+  if (n_points) *n_points = points;
+  if (n_bytes) *n_bytes = bytes;
+  return true;
+}
+
+// The same with the optimiser's poses as objects (Pose::matrix().data() = 16 column-major doubles), or nullptr = the submaps' own.
+template <typename Pose>
+inline bool saveMapPCDFiltered(lsr_handle h, const std::string& path, const std::vector<lsr_submap>& submaps, const Pose* poses_or_null,
+                               float leaf, int data_kind = LSR_PCD_ASCII, bool submaps_on_device = false) {
+  if (!poses_or_null) return saveMapPCDFiltered(h, path, submaps, static_cast<const double*>(nullptr), leaf, data_kind, submaps_on_device);
+  std::vector<double> poses16(16 * submaps.size());
+  for (size_t i = 0; i < submaps.size(); i++) {
+    const auto M = poses_or_null[i].matrix();
+    std::memcpy(poses16.data() + 16 * i, M.data(), 16 * sizeof(double));
+  }
+  return saveMapPCDFiltered(h, path, submaps, poses16.data(), leaf, data_kind, submaps_on_device);
+}
+
 // Whether lsr_load_pcd / lsr_set_input_target_pcd / lsr_decode_pcd of this object read DATA binary_compressed files (what
 // pcl::io::savePCDFileBinaryCompressed writes), the LZF stream inflated on the device (LSR_PCD_READ_COMPRESSED; off by default: such a
 // file is then refused as not implemented).

@@ -25,6 +25,9 @@ PCD_FORMAT_MS, PCD_PIECE_RECORDS = 12, 50
 PCD_PARSE_MS, PCD_READ_PIECE_BYTES, PCD_UNRESOLVED_TOKENS = 13, 52, 53
 PCD_INFLATE_MS, PCD_READ_COMPRESSED = 14, 54
 PCD_DEFLATE_MS = 15
+(MAP_FILTER_BBOX_MS, MAP_FILTER_KEY_MS, MAP_FILTER_SORT_MS, MAP_FILTER_RUNS_MS, MAP_FILTER_CENTROID_MS,
+ MAP_FILTER_WRITE_MS) = range(16, 22)
+MAP_FILTER_KEY_BITS = 55
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2           # lsr_pcd_data
 PCD_DATA_KINDS = {"ascii": PCD_ASCII, "binary": PCD_BINARY, "binary_compressed": PCD_BINARY_COMPRESSED}
 PCD_LZF_CHUNK_BYTES = 4096
@@ -55,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "lsr_sensor_transform_matrix", "lsr_transform_pc2", "lsr_set_input_source_pc2_tf", "lsr_odom_guess",
     "lsr_parse_pcd_header", "lsr_decode_pcd", "lsr_load_pcd", "lsr_set_input_target_pcd",
     "lsr_format_pcd", "lsr_save_pcd", "lsr_save_map_pcd", "lsr_lzf_deflate",
+    "lsr_voxel_grid_filter_map", "lsr_assemble_map_filtered", "lsr_save_map_pcd_filtered",
 ]
 
 
@@ -193,6 +197,12 @@ def load() -> C.CDLL:
     L.lsr_save_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_save_map_pcd.argtypes = [vp, C.c_char_p, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_lzf_deflate.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_voxel_grid_filter_map.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.c_float, vp, C.c_size_t, C.POINTER(Pc2Layout),
+                                            C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_assemble_map_filtered.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, C.c_float, vp, C.c_size_t,
+                                            C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_save_map_pcd_filtered.argtypes = [vp, C.c_char_p, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, C.c_float, C.c_int,
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.lsr_parse_pcd_header.argtypes = [vp, C.c_size_t, C.POINTER(PcdInfo)]
     L.lsr_decode_pcd.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_load_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]

@@ -1,5 +1,6 @@
 // What the host units behind the C ABI share (capi.hip, handle_ops.hip, ndt_align.hip, inputs.hip, sensor_frame.hip, loop_search.hip,
-// map_output.hip, pcd_input.hip and the C ABI at the bottom of deskew.hip): the handle check every entry starts with, the argument
+// map_output.hip, pcd_input.hip and the C ABI at the bottom of deskew.hip and map_filter.hip): the handle check every entry
+// starts with, the argument
 // checks of record_args.hpp reported through set_last_error, the staging of host records on their way in and out, and the functions
 // that cross a unit boundary.
 // Host code only, and none of it does floating-point arithmetic: a unit that holds kernels may include this header (deskew.hip does)

@@ -167,6 +167,9 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_PCD_PARSE_MS: *v = h->pcd_read.parse_ms; return LSR_OK;
     case LSR_PCD_INFLATE_MS: *v = h->pcd_read.inflate_ms; return LSR_OK;
     case LSR_PCD_DEFLATE_MS: *v = h->pcd_deflate.deflate_ms; return LSR_OK;
+    case LSR_MAP_FILTER_BBOX_MS: case LSR_MAP_FILTER_KEY_MS: case LSR_MAP_FILTER_SORT_MS: case LSR_MAP_FILTER_RUNS_MS:
+    case LSR_MAP_FILTER_CENTROID_MS: case LSR_MAP_FILTER_WRITE_MS:
+      *v = h->map_filter.ms[key - LSR_MAP_FILTER_BBOX_MS]; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -250,6 +253,7 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_WAIT_MODE: *v = h->scratch.wait_mode; return LSR_OK;
     case LSR_VOXEL_FILTER_FORM: *v = h->scratch.vg_form; return LSR_OK;
     case LSR_MAP_ASSEMBLY_FORM: *v = h->map_form; return LSR_OK;
+    case LSR_MAP_FILTER_KEY_BITS: *v = h->map_filter.key_bits; return LSR_OK;
     case LSR_PCD_PIECE_RECORDS: *v = h->pcd.piece_records; return LSR_OK;
     case LSR_PCD_READ_PIECE_BYTES: *v = h->pcd_read.piece_bytes; return LSR_OK;
     case LSR_PCD_READ_COMPRESSED: *v = h->pcd_read.read_compressed; return LSR_OK;

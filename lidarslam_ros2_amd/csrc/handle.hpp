@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "deskew.hpp"
 #include "gicp.hpp"
+#include "map_filter.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
 #include "pcd_deflate.hpp"
@@ -101,6 +102,8 @@ struct lsr_handle_s {
   lsr::PcdDeflateState pcd_deflate;   // lsr_format_pcd / lsr_save_pcd / lsr_save_map_pcd (csrc/pcd_deflate.hip): image, slots, stream; kept between calls
 
   lsr::PcdReadState pcd_read;  // lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd (csrc/pcd_read.hip): buffers, kept between calls
+
+  lsr::MapFilterState map_filter;   // lsr_voxel_grid_filter_map / lsr_assemble_map_filtered / lsr_save_map_pcd_filtered (csrc/map_filter.hip): scratch, kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1): one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

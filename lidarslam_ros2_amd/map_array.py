@@ -59,20 +59,29 @@ class MapArray:
         self.submaps.append(sm)
         return sm
 
-    def publish_map(self, reg, out=None):
-        """publishMap (:529-552): every submap moved by its stored pose, concatenated.  -> (records, first_record)."""
-        return reg.assembleMap(self.submaps, None, self.layout, self.layout, out)
+    def publish_map(self, reg, out=None, leaf=None):
+        """publishMap (:529-552): every submap moved by its stored pose, concatenated.  -> (records, first_record).  `leaf`: a leaf
+        size thins the map on the device before it leaves the call (Registration.voxelGridFilterMap) -> (records, None)."""
+        if leaf is None:
+            return reg.assembleMap(self.submaps, None, self.layout, self.layout, out)
+        return reg.assembleMap(self.submaps, None, self.layout, self.layout, out, leaf)
 
-    def modified_map(self, reg, poses, out=None):
+    def modified_map(self, reg, poses, out=None, leaf=None):
         """The map half of doPoseAdjustment (:321-368): every submap moved by the optimiser's estimate for it (4x4 fp64 each).
-        records[first_record[i]:first_record[i + 1]] is modified_map_array.submaps[i].cloud (:343-351).  -> (records, first_record)."""
-        return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
+        records[first_record[i]:first_record[i + 1]] is modified_map_array.submaps[i].cloud (:343-351).  -> (records, first_record).
+        `leaf`: as for publish_map -> (records, None)."""
+        if leaf is None:
+            return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
+        return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out, leaf)
 
-    def save_map(self, reg, path, poses=None, data="ascii") -> int:
+    def save_map(self, reg, path, poses=None, data="ascii", leaf=None) -> int:
         """`pcl::io::savePCDFileASCII("map.pcd", *map_ptr)` at the end of doPoseAdjustment (:369): the map by the stored poses, or by
         the optimiser's `poses` when given (4x4 fp64 each), written to `path` as ASCII PCD with fields x y z intensity — one call into
         the registration object, the map never visits the host as records.  `data`: "ascii" (the default: those bytes), "binary" or
-        "binary_compressed" (the LZF stream compressed on the device).  -> the file's size in bytes."""
+        "binary_compressed" (the LZF stream compressed on the device).  `leaf`: a leaf size thins the map on the device before it is
+        written (Registration.voxelGridFilterMap's records; their number: reg.getSavedMapPoints()).  -> the file's size in bytes."""
+        if leaf is not None:   # the map thinned with this leaf size on the device before it is written
+            return reg.saveMapPCDFile(path, self.submaps, poses, self.layout, data, leaf)
         if data == "ascii":
             return reg.saveMapPCDFileASCII(path, self.submaps, poses, self.layout)
         return reg.saveMapPCDFile(path, self.submaps, poses, self.layout, data)

@@ -416,7 +416,7 @@ class Registration:
         return out[: n_out.value].copy()
 
     # -- the whole map from its submaps ---------------------------------------------
-    def assembleMap(self, submaps, poses=None, in_layout=PC2_XYZI, out_layout=PC2_XYZI, out=None):
+    def assembleMap(self, submaps, poses=None, in_layout=PC2_XYZI, out_layout=PC2_XYZI, out=None, leaf=None):
         """ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of doPoseAdjustment
         (graph_based_slam_component.cpp:321-368) through lsr_assemble_map: every submap moved by its pose, the records concatenated.
         `submaps`: objects with `cloud`, `position`, `orientation` (x y z w) — loop_closure.SubMap; the clouds are record buffers
@@ -424,10 +424,14 @@ class Registration:
         the optimiser's estimates.  Layouts: (point_step, (x, y, z, intensity or None)).  `out`: None = a new buffer, or the uint8
         buffer to write (numpy array or CUDA tensor; a view of a resident map advanced by first_record[k] records appends).
         Returns (records, first_record): (total, out point_step) uint8 — a CUDA tensor when the submaps are CUDA tensors or `out` is
-        one, else a numpy array — and the (n + 1,) int64 index of every submap's first record, the last entry the total."""
+        one, else a numpy array — and the (n + 1,) int64 index of every submap's first record, the last entry the total.
+        `leaf`: None = the raw map as above; a leaf size = that map thinned by voxelGridFilterMap before it leaves the call
+        (lsr_assemble_map_filtered: the raw map stays in HBM) -> (records, None): a leaf mixes submaps, there is no first_record."""
         n = len(submaps)
         if n == 0:
             raise ValueError("assembleMap needs at least one submap")
+        if leaf is not None:
+            return self._assemble_map_filtered(submaps, poses, in_layout, out_layout, out, float(leaf)), None
         li, lo = self._layout(*in_layout), self._layout(*out_layout)
         out_step = int(out_layout[0])
         arr, keep, residency, total, P = self._submap_table(submaps, poses, int(in_layout[0]))
@@ -459,6 +463,72 @@ class Registration:
                                               P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.c_void_p(optr), cap,
                                               C.byref(lo), 1 if out_dev else 0, first, C.byref(n_out)), "assembleMap")
         return flat[: n_out.value * out_step].reshape(n_out.value, out_step), np.array(first[:], np.int64)
+
+    def _out_records(self, out, out_step: int, rows: int, on_device: bool):
+        """The output buffer of a records -> records method -> (buffer, flat uint8 view, pointer, capacity in records, on_device).
+        out: None = a new uninitialised buffer of `rows` records (a CUDA tensor when on_device), else the uint8 buffer to write."""
+        if out is None:
+            if on_device:
+                import torch
+
+                out = torch.empty((max(rows, 1), out_step), dtype=torch.uint8, device=torch.device("cuda", self._device))
+            else:
+                out = np.empty((max(rows, 1), out_step), np.uint8)
+        if _is_torch_cuda(out):
+            if not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out must be a contiguous uint8 buffer")
+            _order_after_torch(self, out)
+            return out, out.view(-1), out.data_ptr(), out.numel() // out_step, True
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError("out must be a writeable contiguous uint8 buffer")
+        return out, out.reshape(-1), out.ctypes.data, out.nbytes // out_step, False
+
+    @staticmethod
+    def _trimmed(flat, count: int, out_step: int, capacity: int, own: bool):
+        """The first `count` records of a result buffer; one this object allocated for many more is not kept alive by the view."""
+        view = flat[: count * out_step].reshape(count, out_step)
+        if own and 2 * count < capacity:
+            return view.clone() if _is_torch_cuda(view) else view.copy()
+        return view
+
+    def _assemble_map_filtered(self, submaps, poses, in_layout, out_layout, out, leaf: float):
+        n = len(submaps)
+        li, lo = self._layout(*in_layout), self._layout(*out_layout)
+        out_step = int(out_layout[0])
+        arr, keep, residency, total, P = self._submap_table(submaps, poses, int(in_layout[0]))
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        own = out is None
+        _, flat, optr, cap, out_dev = self._out_records(out, out_step, total, bool(residency))
+        n_out = C.c_size_t()
+        capi.check(self._lib.lsr_assemble_map_filtered(self._h, arr, n, C.byref(li), 1 if residency else 0,
+                                                       P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.c_float(leaf),
+                                                       C.c_void_p(optr), cap, C.byref(lo), 1 if out_dev else 0, C.byref(n_out)),
+                   "assembleMap")
+        return self._trimmed(flat, int(n_out.value), out_step, cap, own)
+
+    def voxelGridFilterMap(self, records, leaf: float, layout=PC2_XYZI, out_layout=PC2_XYZI, out=None):
+        """pcl::VoxelGrid(leaf).filter for a map-sized cloud through lsr_voxel_grid_filter_map: records in, records out, on the device,
+        the leaf index carried in 64 bits (a map of kilometres at a 0.1 m leaf, which pcl::VoxelGrid and voxelGridFilterPointCloud2
+        refuse).  One record per occupied leaf in ascending leaf index, all four fields averaged in float in input order; wherever
+        voxelGridFilterPointCloud2 accepts the cloud, the same bytes.  `records`: a record buffer of `layout` — numpy array (->
+        uint8 numpy array) or CUDA tensor (-> uint8 CUDA tensor, nothing leaves HBM).  `out`: None = a new buffer, or the uint8 buffer
+        to write (numpy array or CUDA tensor).  -> (m, out point_step) uint8."""
+        li, lo = self._layout(*layout), self._layout(*out_layout)
+        out_step = int(out_layout[0])
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
+        own = out is None
+        _, flat, optr, cap, out_dev = self._out_records(out, out_step, n, dev)
+        n_out = C.c_size_t()
+        capi.check(self._lib.lsr_voxel_grid_filter_map(self._h, ptr, n, C.byref(li), 1 if dev else 0, C.c_float(leaf), C.c_void_p(optr), cap,
+                                                       C.byref(lo), 1 if out_dev else 0, C.byref(n_out)), "voxelGridFilterMap")
+        return self._trimmed(flat, int(n_out.value), out_step, cap, own)
+
+    def mapFilterKeyBits(self) -> int:
+        """The bits of the largest leaf index of the last map filter on this object (LSR_MAP_FILTER_KEY_BITS); above 32 the index was
+        sorted as two words; 0 = none yet."""
+        return self._geti(capi.MAP_FILTER_KEY_BITS)
 
     def _submap_table(self, submaps, poses, in_step: int):
         """The lsr_submap array of assembleMap / saveMapPCDFileASCII -> (array, keepalives, on_device, total records, column-major
@@ -531,10 +601,13 @@ class Registration:
                    "savePCDFileASCII")
         return int(size.value)
 
-    def saveMapPCDFileASCII(self, path, submaps, poses=None, in_layout=PC2_XYZI) -> int:
+    def saveMapPCDFileASCII(self, path, submaps, poses=None, in_layout=PC2_XYZI, leaf=None) -> int:
         """`if (do_save_map) pcl::io::savePCDFileASCII("map.pcd", *map_ptr)` (graph_based_slam_component.cpp:369) in one call
         (lsr_save_map_pcd_ascii): the submaps moved by their poses (`poses`: None = their own, or the optimiser's, as for assembleMap)
-        into a map that stays on the device, and that map written as text.  Returns the file's size in bytes."""
+        into a map that stays on the device, and that map written as text.  Returns the file's size in bytes.  `leaf`: as for
+        saveMapPCDFile."""
+        if leaf is not None:
+            return self.saveMapPCDFile(path, submaps, poses, in_layout, "ascii", leaf)
         n = len(submaps)
         if n == 0:
             raise ValueError("saveMapPCDFileASCII needs at least one submap")
@@ -599,9 +672,11 @@ class Registration:
         capi.check(self._lib.lsr_save_pcd(self._h, os.fsencode(path), ptr, n, C.byref(lay), 1 if dev else 0, kind, C.byref(size)), "savePCDFile")
         return int(size.value)
 
-    def saveMapPCDFile(self, path, submaps, poses=None, in_layout=PC2_XYZI, data="ascii") -> int:
+    def saveMapPCDFile(self, path, submaps, poses=None, in_layout=PC2_XYZI, data="ascii", leaf=None) -> int:
         """saveMapPCDFileASCII with a body kind (lsr_save_map_pcd): the submaps moved by their poses into a map that stays on the device,
-        and that map written as `data`.  Returns the file's size in bytes."""
+        and that map written as `data`.  Returns the file's size in bytes.  `leaf`: None = the raw map; a leaf size = the map
+        thinned by voxelGridFilterMap on the device before it is written (lsr_save_map_pcd_filtered; the number of records in the
+        file is then getSavedMapPoints())."""
         kind = self._pcd_kind(data)
         n = len(submaps)
         if n == 0:
@@ -612,10 +687,21 @@ class Registration:
         if dev_holders:
             _order_after_torch(self, dev_holders[-1])
         size = C.c_size_t()
+        if leaf is not None:
+            n_pts = C.c_size_t()
+            capi.check(self._lib.lsr_save_map_pcd_filtered(self._h, os.fsencode(path), arr, n, C.byref(li), 1 if residency else 0,
+                                                           P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None,
+                                                           C.c_float(float(leaf)), kind, C.byref(n_pts), C.byref(size)), "saveMapPCDFile")
+            self._saved_map_points = int(n_pts.value)
+            return int(size.value)
         capi.check(self._lib.lsr_save_map_pcd(self._h, os.fsencode(path), arr, n, C.byref(li), 1 if residency else 0,
                                               P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, kind, C.byref(size)),
                    "saveMapPCDFile")
         return int(size.value)
+
+    def getSavedMapPoints(self) -> int:
+        """The number of records the last saveMapPCDFile(..., leaf=...) on this object wrote (0 = none yet)."""
+        return int(getattr(self, "_saved_map_points", 0))
 
     def lzfDeflate(self, image):
         """The compressor alone (lsr_lzf_deflate): the LZF stream of `image` — bytes / uint8 numpy array (-> uint8 numpy array) or CUDA
