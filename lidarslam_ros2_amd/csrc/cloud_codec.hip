@@ -20,61 +20,40 @@ namespace lsr {
 namespace {
 
 // The same keys with the grid dimensions worked out ON THE DEVICE from the bounding-box records the ingest pass left in device memory
-// (pc2_ingest): every workgroup folds the (<= 256) records itself — the arithmetic is voxel_grid_filter's host code, operation for
-// operation — and workgroup 0 leaves {sentinel, finite points, VG_FLAG_*, key bits} in dims[0..3] for the kernels behind the sort.
-// The host never sees the box: it enqueues key + sort + run heads + centroids without a wait in between.
-// dims folded from the records of the ingest pass by ALL 256 threads of a workgroup (one barrier inside)
+// (pc2_ingest): every workgroup folds the (<= 256) records itself — the arithmetic is voxel_grid_filter's host code: both call
+// grid_dims and bits_for of voxel_device.hpp — and workgroup 0 leaves {sentinel, finite points, VG_FLAG_*, key bits} in dims[0..3]
+// for the kernels behind the sort.  The host never sees the box: it enqueues key + sort + run heads + centroids without a wait in
+// between.
+// dims folded from the records of the ingest pass by ALL 256 threads of a workgroup (one barrier inside: box_fold_block's)
 struct VgDims { int mb[3], dv[3]; unsigned int sentinel, flags, n_finite; int bits; };
 __device__ __forceinline__ VgDims vg_fold_dims(const unsigned long long* __restrict__ parts, int nparts, float inv_leaf, int planned_bits) {
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int tid = threadIdx.x, w = tid >> 6;
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned int cnt = 0;
+  const int tid = threadIdx.x;
+  BoxAcc box;
   if (tid < nparts) {
     const unsigned long long* P = parts + (size_t)tid * 8;
 #pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = __uint_as_float((unsigned int)P[k]); mx[k] = __uint_as_float((unsigned int)P[3 + k]); }
-    cnt = (unsigned int)P[6];
+    for (int k = 0; k < 3; k++) { box.mn[k] = __uint_as_float((unsigned int)P[k]); box.mx[k] = __uint_as_float((unsigned int)P[3 + k]); }
+    box.cnt = (unsigned int)P[6];
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64)); }
-    cnt += __shfl_xor(cnt, m, 64);
-  }
-  if ((tid & 63) == 0) {
-    for (int k = 0; k < 3; k++) { s_mn[w][k] = mn[k]; s_mx[w][k] = mx[k]; }
-    s_cnt[w] = cnt;
-  }
-  __syncthreads();
+  const BoxFolded F = box_fold_block(box);
   VgDims D;
-  D.n_finite = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+  D.n_finite = F.count();
   for (int k = 0; k < 3; k++) { D.mb[k] = 0; D.dv[k] = 0; }
   D.sentinel = 0u; D.flags = 0u; D.bits = 1;
   if (D.n_finite != 0u) {
-    long long vol = 1;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const float lo = fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k]));
-      const float hi = fmaxf(fmaxf(s_mx[0][k], s_mx[1][k]), fmaxf(s_mx[2][k], s_mx[3][k]));
-      vol *= (long long)((hi - lo) * inv_leaf) + 1;
-      D.mb[k] = (int)floorf(lo * inv_leaf);
-      D.dv[k] = (int)floorf(hi * inv_leaf) - D.mb[k] + 1;
-    }
-    if (vol > (long long)INT32_MAX) D.flags |= VG_FLAG_OVERFLOW;
+    const float lo[3] = {F.lo(0), F.lo(1), F.lo(2)}, hi[3] = {F.hi(0), F.hi(1), F.hi(2)};
+    const GridDims G = grid_dims(lo, hi, inv_leaf);
+    for (int k = 0; k < 3; k++) { D.mb[k] = G.min_b[k]; D.dv[k] = G.div_b[k]; }
+    if (G.volume > (long long)INT32_MAX) D.flags |= VG_FLAG_OVERFLOW;
     D.sentinel = (unsigned int)((long long)D.dv[0] * D.dv[1] * D.dv[2]);
-    while (D.bits < 32 && (D.sentinel >> D.bits) != 0u) D.bits++;
+    D.bits = bits_for(D.sentinel);
     if (D.bits > planned_bits) D.flags |= VG_FLAG_REPLAN;
   }
   return D;
 }
 __device__ __forceinline__ unsigned int vg_key(const VgDims& D, float inv_leaf, float px, float py, float pz) {
-  if (D.flags != 0u || !(isfinite(px) && isfinite(py) && isfinite(pz))) return D.sentinel;
-  const int i0 = (int)(floorf(px * inv_leaf) - (float)D.mb[0]);
-  const int i1 = (int)(floorf(py * inv_leaf) - (float)D.mb[1]);
-  const int i2 = (int)(floorf(pz * inv_leaf) - (float)D.mb[2]);
-  return (unsigned int)(i0 + i1 * D.dv[0] + i2 * (D.dv[0] * D.dv[1]));
+  if (D.flags != 0u) return D.sentinel;
+  return leaf_key<int>(px, py, pz, inv_leaf, D.mb[0], D.mb[1], D.mb[2], D.dv[0], D.dv[0] * D.dv[1], D.sentinel);
 }
 
 __global__ __launch_bounds__(256) void leaf_key_dims_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -270,17 +249,12 @@ int voxel_grid_filter(const DeviceCloud& cloud, float leaf, DeviceCloud& out, Bu
   st = cloud_bbox(cloud, mn, mx, &n_finite, sc, stream);
   if (st) return st;
   if (n_finite == 0) return out.resize(0, cloud.has_i);
-  int64_t d[3];
-  for (int k = 0; k < 3; k++) d[k] = (int64_t)((mx[k] - mn[k]) * inv_leaf) + 1;
-  if (d[0] * d[1] * d[2] > (int64_t)INT32_MAX) {  // PCL: "Leaf size is too small for the input dataset"
+  const GridDims G = grid_dims(mn, mx, inv_leaf);
+  if (G.volume > (long long)INT32_MAX) {  // PCL: "Leaf size is too small for the input dataset"
     set_last_error("voxel index space exceeds int32: leaf size too small for the cloud extent");
     return LSR_ERR_INDEX_OVERFLOW;
   }
-  int min_b[3], div_b[3];
-  for (int k = 0; k < 3; k++) {
-    min_b[k] = (int)floorf(mn[k] * inv_leaf);
-    div_b[k] = (int)floorf(mx[k] * inv_leaf) - min_b[k] + 1;
-  }
+  const int *min_b = G.min_b, *div_b = G.div_b;
   const unsigned int sentinel = (unsigned int)((int64_t)div_b[0] * div_b[1] * div_b[2]);  // one past the last leaf index
   sc.vg_bits_hint = bits_for(sentinel);
   sc.vg_hint_leaf = leaf;
@@ -354,8 +328,7 @@ __global__ __launch_bounds__(256) void pc2_ingest_kernel(const unsigned char* __
                                                          float* __restrict__ w, int do_range, double rmin, double rmax,
                                                          unsigned long long* __restrict__ parts_dev, BuildMailbox* __restrict__ mb,
                                                          unsigned int token, const SensorTf12 tf) {
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned int cnt = 0;
+  BoxAcc box;
   const int step_pts = gridDim.x * blockDim.x;
   for (int i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += 4 * step_pts) {  // four records per trip in flight
     float p[4][4];
@@ -392,36 +365,10 @@ __global__ __launch_bounds__(256) void pc2_ingest_kernel(const unsigned char* __
       }
       x[i] = p[u][0]; y[i] = p[u][1]; z[i] = p[u][2];
       if (w) w[i] = p[u][3];
-      if (!(isfinite(p[u][0]) && isfinite(p[u][1]) && isfinite(p[u][2]))) continue;
-      cnt++;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], p[u][k]); mx[k] = fmaxf(mx[k], p[u][k]); }
+      box.add(p[u][0], p[u][1], p[u][2]);
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64)); }
-    cnt += __shfl_xor(cnt, m, 64);
-  }
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    for (int k = 0; k < 3; k++) { s_mn[wv][k] = mn[k]; s_mx[wv][k] = mx[k]; }
-    s_cnt[wv] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < BBOX_GRANULES) {
-    const int k = threadIdx.x;
-    unsigned int bits;
-    if (k < 3) bits = __float_as_uint(fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k])));
-    else if (k < 6) bits = __float_as_uint(fmaxf(fmaxf(s_mx[0][k - 3], s_mx[1][k - 3]), fmaxf(s_mx[2][k - 3], s_mx[3][k - 3])));
-    else bits = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    const unsigned long long g = ((unsigned long long)token << 32) | bits;
-    parts_dev[(size_t)blockIdx.x * 8 + k] = g;
-    __hip_atomic_store(&mb->part[blockIdx.x].g[k], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  box_publish(box_fold_block(box), &mb->part[blockIdx.x], token, parts_dev + (size_t)blockIdx.x * 8, nullptr);
 }
 }  // namespace
 

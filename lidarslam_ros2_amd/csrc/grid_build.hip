@@ -25,8 +25,7 @@ namespace {
 // reduction itself takes 4.
 __global__ __launch_bounds__(256) void bbox_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                    const float* __restrict__ z, int n, BuildMailbox* __restrict__ mb, unsigned int token) {
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned int cnt = 0;
+  BoxAcc box;
   const int step = gridDim.x * blockDim.x;
   for (int i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += 4 * step) {  // four points per trip: 12 loads in flight
     float p[4][3];
@@ -37,41 +36,9 @@ __global__ __launch_bounds__(256) void bbox_kernel(const float* __restrict__ x, 
       p[u][0] = in ? x[i] : NAN; p[u][1] = in ? y[i] : NAN; p[u][2] = in ? z[i] : NAN;
     }
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
-      if (!(isfinite(p[u][0]) && isfinite(p[u][1]) && isfinite(p[u][2]))) continue;
-      cnt++;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        mn[k] = fminf(mn[k], p[u][k]);
-        mx[k] = fmaxf(mx[k], p[u][k]);
-      }
-    }
+    for (int u = 0; u < 4; u++) box.add(p[u][0], p[u][1], p[u][2]);
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64));
-      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64));
-    }
-    cnt += __shfl_xor(cnt, m, 64);
-  }
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    for (int k = 0; k < 3; k++) { s_mn[w][k] = mn[k]; s_mx[w][k] = mx[k]; }
-    s_cnt[w] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < BBOX_GRANULES) {
-    const int k = threadIdx.x;
-    unsigned int bits;
-    if (k < 3) bits = __float_as_uint(fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k])));
-    else if (k < 6) bits = __float_as_uint(fmaxf(fmaxf(s_mx[0][k - 3], s_mx[1][k - 3]), fmaxf(s_mx[2][k - 3], s_mx[3][k - 3])));
-    else bits = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    __hip_atomic_store(&mb->part[blockIdx.x].g[k], ((unsigned long long)token << 32) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  box_publish(box_fold_block(box), &mb->part[blockIdx.x], token, nullptr, nullptr);
 }
 
 // K1: one wave per leaf; lanes stride the leaf's points (stable-sorted => ascending point index),
@@ -351,16 +318,15 @@ int ndt_grid_geometry(const DeviceCloud& cloud, float leaf, VoxelGridDev& grid, 
   int st = cloud_bbox_end(cloud, mn, mx, &n_finite, sc, stream);   // host poll #1
   if (st) return st;
   if (n_finite == 0) return LSR_OK;  // no finite point: empty grid
-  int64_t d[3];
-  for (int k = 0; k < 3; k++) d[k] = (int64_t)((mx[k] - mn[k]) * inv_leaf) + 1;
-  if (d[0] * d[1] * d[2] > (int64_t)INT32_MAX) {
+  const GridDims G = grid_dims(mn, mx, inv_leaf);
+  if (G.volume > (long long)INT32_MAX) {
     set_last_error("voxel index space exceeds int32: leaf size too small for the target extent");
     return LSR_ERR_INDEX_OVERFLOW;
   }
   for (int k = 0; k < 3; k++) {
-    grid.min_b[k] = (int)floorf(mn[k] * inv_leaf);
-    grid.max_b[k] = (int)floorf(mx[k] * inv_leaf);
-    grid.div_b[k] = grid.max_b[k] - grid.min_b[k] + 1;
+    grid.min_b[k] = G.min_b[k];
+    grid.div_b[k] = G.div_b[k];
+    grid.max_b[k] = G.min_b[k] + G.div_b[k] - 1;
   }
   grid.ncells = (size_t)grid.div_b[0] * grid.div_b[1] * grid.div_b[2];
   *path = (grid.ncells <= (size_t)VG_DENSE_MAX_CELLS && !sc.force_sort_path) ? 1 : 2;

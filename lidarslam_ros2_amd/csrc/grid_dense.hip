@@ -25,6 +25,7 @@
 
 #include "grid_device.hpp"
 #include "ndt.hpp"
+#include "voxel_device.hpp"
 
 namespace lsr {
 
@@ -59,12 +60,6 @@ namespace {
 constexpr int VG_CHUNK = 4096;  // points per workgroup: 4 waves x 16 steps x 64 lanes
 constexpr int VG_STEPS = 16;
 
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // key = linear leaf index exactly as VoxelGridCovariance computes it; non-finite points get the
 // sentinel bin `ncells` (sorted last, never a leaf)
 __device__ __forceinline__ void vg_hist_kernel_body(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
@@ -86,14 +81,8 @@ __device__ __forceinline__ void vg_hist_kernel_body(const float* __restrict__ x,
   for (int j = 0; j < VG_CHUNK / 256; j++) {
     const int i = base + j * 256 + tid;
     if (i < n) {
-      unsigned int k = (unsigned int)ncells;
-      if (isfinite(px[j]) && isfinite(py[j]) && isfinite(pz[j])) {
-        const int i0 = (int)(floorf(px[j] * inv_leaf) - (float)mb0);
-        const int i1 = (int)(floorf(py[j] * inv_leaf) - (float)mb1);
-        const int i2 = (int)(floorf(pz[j] * inv_leaf) - (float)mb2);
-        k = (unsigned int)(i0 + i1 * mul1 + i2 * mul2);
-        if (k >= (unsigned int)ncells) k = (unsigned int)ncells;  // cannot happen for a bbox built from the same floats
-      }
+      unsigned int k = leaf_key<int>(px[j], py[j], pz[j], inv_leaf, mb0, mb1, mb2, mul1, mul2, (unsigned int)ncells);
+      if (k >= (unsigned int)ncells) k = (unsigned int)ncells;  // cannot happen for a bbox built from the same floats
       keys[i] = (unsigned short)k;
       atomicAdd(&s_hist[k], 1u);
     }
@@ -282,7 +271,7 @@ __device__ __forceinline__ void vg_leaf_kernel_body(const float* __restrict__ sx
     s[6] += py * py; s[7] += py * pz; s[8] += pz * pz;
   }
 #pragma unroll
-  for (int k = 0; k < 9; k++) s[k] = wave_sum64(s[k]);
+  for (int k = 0; k < 9; k++) s[k] = wave_sum(s[k]);
   if (lane != 0) return;
   if (SUMS_ONLY) {
 #pragma unroll
@@ -345,8 +334,7 @@ static_assert(sizeof(VgGroup) <= 3800, "a group's parameters must fit the kernel
 __global__ __launch_bounds__(256) void vg_ingest_group_kernel(const VgGroup g) {
   const VgMember& M = g.m[blockIdx.y];
   if ((int)blockIdx.x >= M.ingest_blocks) return;
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned int cnt = 0;
+  BoxAcc box;
   const int step = M.ingest_blocks * 256;
   // records of 16-byte aligned stride (pcl::PointXYZI: 32 bytes) are read as ONE 16-byte load per point, anything else as three
   const bool wide = ((M.stride & 15) == 0) && ((reinterpret_cast<size_t>(M.aos) & 15) == 0);
@@ -371,38 +359,10 @@ __global__ __launch_bounds__(256) void vg_ingest_group_kernel(const VgGroup g) {
     for (int u = 0; u < 4; u++) {
       const int i = i0 + u * step;
       if (i < M.n) { M.x[i] = p[u][0]; M.y[i] = p[u][1]; M.z[i] = p[u][2]; }
-      if (!(isfinite(p[u][0]) && isfinite(p[u][1]) && isfinite(p[u][2]))) continue;
-      cnt++;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], p[u][k]); mx[k] = fmaxf(mx[k], p[u][k]); }
+      box.add(p[u][0], p[u][1], p[u][2]);
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64));
-      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64));
-    }
-    cnt += __shfl_xor(cnt, m, 64);
-  }
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    for (int k = 0; k < 3; k++) { s_mn[w][k] = mn[k]; s_mx[w][k] = mx[k]; }
-    s_cnt[w] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < BBOX_GRANULES) {   // seven self-validating granules, no fence (common.hpp: BboxPart)
-    const int k = threadIdx.x;
-    unsigned int bits;
-    if (k < 3) bits = __float_as_uint(fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k])));
-    else if (k < 6) bits = __float_as_uint(fmaxf(fmaxf(s_mx[0][k - 3], s_mx[1][k - 3]), fmaxf(s_mx[2][k - 3], s_mx[3][k - 3])));
-    else bits = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    __hip_atomic_store(&M.mb->part[blockIdx.x].g[k], ((unsigned long long)M.bbox_token << 32) | bits, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  box_publish(box_fold_block(box), &M.mb->part[blockIdx.x], M.bbox_token, nullptr, nullptr);   // seven self-validating granules, no fence
 }
 __global__ __launch_bounds__(256) void vg_hist_group_kernel(const VgGroup g) {
   const VgMember& M = g.m[blockIdx.y];

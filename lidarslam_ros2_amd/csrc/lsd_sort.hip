@@ -17,6 +17,7 @@
 // run-length encode + exclusive scan + a publishing launch.
 #include "handle.hpp"
 #include "sort.hpp"
+#include "voxel_device.hpp"
 
 namespace lsr {
 
@@ -222,17 +223,10 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const unsigned i
 
 // ---- runs of equal keys in the sorted sequence ---------------------------------------------------------------------------
 constexpr int RUN_CHUNK = 256;   // keys per workgroup: one per thread (a head's loop over its run is the long pole: keep it one per lane)
-__device__ __forceinline__ bool is_head(const unsigned int* __restrict__ keys, int i) { return i == 0 || keys[i] != keys[i - 1]; }
-
+// (the walk itself — heads, ranks, the centroid of a run — is voxel_device.hpp's, shared with the map filter)
 __global__ __launch_bounds__(256) void rs_heads_count_kernel(const unsigned int* __restrict__ keys, int n, int* __restrict__ block_heads) {
-  __shared__ int s_w[4];
-  const int i = blockIdx.x * RUN_CHUNK + threadIdx.x;
-  int c = (i < n && is_head(keys, i)) ? 1 : 0;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) block_heads[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const int c = run_heads_in_block(KeysU32{keys}, (int)(blockIdx.x * RUN_CHUNK + threadIdx.x), n);
+  if (threadIdx.x == 0) block_heads[blockIdx.x] = c;
 }
 
 // one workgroup: exclusive scan of the per-workgroup head counts; the total goes to the host mailbox (value + token)
@@ -275,53 +269,28 @@ __global__ __launch_bounds__(256) void rs_centroid_kernel(const unsigned int* __
                                                           const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
                                                           const float* __restrict__ w /*nullable*/, float* __restrict__ ox,
                                                           float* __restrict__ oy, float* __restrict__ oz, float* __restrict__ ow) {
-  __shared__ int s_w[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const KeysU32 K{keys};
   const int i = blockIdx.x * RUN_CHUNK + threadIdx.x;
-  const bool head = (i < n) && is_head(keys, i);
-  const unsigned long long heads = __ballot(head);
-  if (lane == 0) s_w[wave] = __popcll(heads);
-  __syncthreads();
+  const bool head = (i < n) && run_is_head(K, i);
+  const int r = run_rank_in_block(head, block_base);
   if (!head) return;
-  int r = block_base[blockIdx.x] + __popcll(heads & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
-  for (int k = 0; k < wave; k++) r += s_w[k];
   const unsigned int k = keys[i];
   const unsigned int sentinel = sentinel_dev ? *sentinel_dev : sentinel_arg;
   if (k == sentinel) return;
-  float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
-  int j = i;
-  // the additions are a chain by definition (float, in index order); the gathers that feed them are not: four points in flight
-  for (; j + 3 < n && keys[j + 3] == k; j += 4) {   // sorted keys: keys[j + 3] == k implies the three before it
-    const int p0 = order[j], p1 = order[j + 1], p2 = order[j + 2], p3 = order[j + 3];
-    const float x0 = x[p0], y0 = y[p0], z0 = z[p0], x1 = x[p1], y1 = y[p1], z1 = z[p1];
-    const float x2 = x[p2], y2 = y[p2], z2 = z[p2], x3 = x[p3], y3 = y[p3], z3 = z[p3];
-    sx += x0; sy += y0; sz += z0; sx += x1; sy += y1; sz += z1; sx += x2; sy += y2; sz += z2; sx += x3; sy += y3; sz += z3;
-    if (w) { const float w0 = w[p0], w1 = w[p1], w2 = w[p2], w3 = w[p3]; sw += w0; sw += w1; sw += w2; sw += w3; }
-  }
-  for (; j < n && keys[j] == k; j++) {
-    const int pi = order[j];
-    sx += x[pi]; sy += y[pi]; sz += z[pi];
-    if (w) sw += w[pi];
-  }
-  const float m = (float)(j - i);
-  ox[r] = sx / m; oy[r] = sy / m; oz[r] = sz / m;
-  if (ow) ow[r] = w ? sw / m : 0.f;
+  float c[4];
+  run_centroid(K, k, PlanePoints{x, y, z, w}, order, i, n, c);
+  ox[r] = c[0]; oy[r] = c[1]; oz[r] = c[2];
+  if (ow) ow[r] = c[3];
 }
 
 // The runs as a table (what a run-length encode followed by an exclusive scan gives): run r in key order has
 // key run_key[r] and covers the sorted positions [run_off[r], run_off[r + 1]); run_off[number of runs] = n closes the table.
 __global__ __launch_bounds__(256) void rs_runs_table_kernel(const unsigned int* __restrict__ keys, int n, const int* __restrict__ block_base,
                                                             unsigned int* __restrict__ run_key, int* __restrict__ run_off) {
-  __shared__ int s_w[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * RUN_CHUNK + threadIdx.x;
-  const bool head = (i < n) && is_head(keys, i);
-  const unsigned long long heads = __ballot(head);
-  if (lane == 0) s_w[wave] = __popcll(heads);
-  __syncthreads();
+  const bool head = (i < n) && run_is_head(KeysU32{keys}, i);
+  const int r = run_rank_in_block(head, block_base);   // heads before this position
   if (i >= n) return;
-  int r = block_base[blockIdx.x] + __popcll(heads & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));   // heads before this position
-  for (int k = 0; k < wave; k++) r += s_w[k];
   if (head) { run_key[r] = keys[i]; run_off[r] = i; }
   if (i == n - 1) run_off[r + (head ? 1 : 0)] = n;   // r counts the heads BEFORE i: the table has r (+ 1 if i is a head itself) runs
 }

@@ -15,6 +15,8 @@
 //   centroids (one thread per head, float sums in ascending input index, four gathers in flight) -> the output records, word by word.
 // Arithmetic: one float multiply per coordinate, a floor, a float subtraction (exact below MF_CELL_LIMIT), float additions in index
 // order and one float division per field: nothing a contraction could fuse (the unit is built with -ffp-contract=off all the same).
+// That arithmetic, the box fold and the run walk are the int32 filter's own text (voxel_device.hpp), instantiated here over records,
+// (high, low) key words and int64 products.
 #include "map_filter.hpp"
 
 #include <algorithm>
@@ -22,6 +24,7 @@
 
 #include "api_internal.hpp"
 #include "sort.hpp"
+#include "voxel_device.hpp"
 
 namespace lsr {
 
@@ -29,13 +32,10 @@ namespace {
 
 constexpr int MF_CHUNK = 256;   // sorted keys per workgroup of the run finder and of the centroids: one per thread
 
-__device__ __forceinline__ float mf_field(const unsigned char* __restrict__ rec, int off) { return *reinterpret_cast<const float*>(rec + off); }
-
 // per workgroup {min xyz, max xyz, finite points, -} of the finite points it walked (float bits): parts[8 * workgroup + k]
 __global__ __launch_bounds__(256) void mf_bbox_kernel(const unsigned char* __restrict__ data, int step, int ox, int oy, int oz, size_t n,
                                                       unsigned int* __restrict__ parts) {
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned int cnt = 0;
+  BoxAcc box;
   const size_t stride = (size_t)gridDim.x * 256;
   for (size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x; i0 < n; i0 += 4 * stride) {   // four records per trip in flight
     float p[4][3];
@@ -44,46 +44,20 @@ __global__ __launch_bounds__(256) void mf_bbox_kernel(const unsigned char* __res
       const size_t i = i0 + u * stride;
       if (i < n) {
         const unsigned char* rec = data + i * (size_t)step;
-        p[u][0] = mf_field(rec, ox); p[u][1] = mf_field(rec, oy); p[u][2] = mf_field(rec, oz);
+        p[u][0] = record_field(rec, ox); p[u][1] = record_field(rec, oy); p[u][2] = record_field(rec, oz);
       } else {
         p[u][0] = p[u][1] = p[u][2] = NAN;
       }
     }
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
-      if (!(isfinite(p[u][0]) && isfinite(p[u][1]) && isfinite(p[u][2]))) continue;
-      cnt++;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], p[u][k]); mx[k] = fmaxf(mx[k], p[u][k]); }
-    }
+    for (int u = 0; u < 4; u++) box.add(p[u][0], p[u][1], p[u][2]);
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64)); }
-    cnt += __shfl_xor(cnt, m, 64);
-  }
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    for (int k = 0; k < 3; k++) { s_mn[wv][k] = mn[k]; s_mx[wv][k] = mx[k]; }
-    s_cnt[wv] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    const int k = threadIdx.x;
-    unsigned int bits = 0u;
-    if (k < 3) bits = __float_as_uint(fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k])));
-    else if (k < 6) bits = __float_as_uint(fmaxf(fmaxf(s_mx[0][k - 3], s_mx[1][k - 3]), fmaxf(s_mx[2][k - 3], s_mx[3][k - 3])));
-    else if (k == 6) bits = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    parts[(size_t)blockIdx.x * 8 + k] = bits;
-  }
+  box_publish(box_fold_block(box), nullptr, 0u, nullptr, parts + (size_t)blockIdx.x * 8);
 }
 
-// The leaf index of every record, as voxel_grid_filter forms it (build_kernels.hpp: leaf_key_kernel) with the products in int64; a
-// record with a non-finite coordinate gets `cells`, one past the last index.  lo_sort: the low word where the sort reads it; for a
-// wide index (hi_keep != null) both words are also kept where the sort does not write.
+// The leaf index of every record, as voxel_grid_filter forms it (voxel_device.hpp: leaf_key) with the products in int64; a record
+// with a non-finite coordinate gets `cells`, one past the last index.  lo_sort: the low word where the sort reads it; for a wide
+// index (hi_keep != null) both words are also kept where the sort does not write.
 __global__ __launch_bounds__(256) void mf_key_kernel(const unsigned char* __restrict__ data, int step, int ox, int oy, int oz, size_t n,
                                                      float inv_leaf, int mb0, int mb1, int mb2, long long mul1, long long mul2,
                                                      unsigned long long cells, unsigned int* __restrict__ lo_sort,
@@ -91,14 +65,8 @@ __global__ __launch_bounds__(256) void mf_key_kernel(const unsigned char* __rest
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const unsigned char* rec = data + i * (size_t)step;
-  const float px = mf_field(rec, ox), py = mf_field(rec, oy), pz = mf_field(rec, oz);
-  unsigned long long k = cells;
-  if (isfinite(px) && isfinite(py) && isfinite(pz)) {
-    const int i0 = (int)(floorf(px * inv_leaf) - (float)mb0);
-    const int i1 = (int)(floorf(py * inv_leaf) - (float)mb1);
-    const int i2 = (int)(floorf(pz * inv_leaf) - (float)mb2);
-    k = (unsigned long long)((long long)i0 + (long long)i1 * mul1 + (long long)i2 * mul2);
-  }
+  const unsigned long long k =
+      leaf_key<long long>(record_field(rec, ox), record_field(rec, oy), record_field(rec, oz), inv_leaf, mb0, mb1, mb2, mul1, mul2, cells);
   lo_sort[i] = (unsigned int)k;
   if (hi_keep) { lo_keep[i] = (unsigned int)k; hi_keep[i] = (unsigned int)(k >> 32); }
 }
@@ -110,73 +78,35 @@ __global__ __launch_bounds__(256) void mf_gather_kernel(const unsigned int* __re
   if (j < n) out[j] = src[order[j]];
 }
 
-__device__ __forceinline__ bool mf_same(const unsigned int* __restrict__ lo, const unsigned int* __restrict__ hi, size_t a, size_t b) {
-  return lo[a] == lo[b] && (!hi || hi[a] == hi[b]);
-}
-__device__ __forceinline__ bool mf_is_head(const unsigned int* __restrict__ lo, const unsigned int* __restrict__ hi, size_t j) {
-  return j == 0 || !mf_same(lo, hi, j, j - 1);
-}
-
 // heads of the runs of equal (high, low) pairs per chunk of MF_CHUNK sorted keys; workgroup 0 also zeroes the closing entry
 // block_heads[gridDim.x], whose exclusive prefix is the number of runs
 __global__ __launch_bounds__(256) void mf_heads_kernel(const unsigned int* __restrict__ lo, const unsigned int* __restrict__ hi, size_t n,
                                                        int* __restrict__ block_heads) {
-  __shared__ int s_w[4];
-  const size_t j = (size_t)blockIdx.x * MF_CHUNK + threadIdx.x;
-  int c = (j < n && mf_is_head(lo, hi, j)) ? 1 : 0;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-  __syncthreads();
+  const int c = run_heads_in_block(KeysHiLo{lo, hi}, (size_t)blockIdx.x * MF_CHUNK + threadIdx.x, n);
   if (threadIdx.x == 0) {
-    block_heads[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    block_heads[blockIdx.x] = c;
     if (blockIdx.x == 0) block_heads[gridDim.x] = 0;
   }
 }
 
-// Every head sums its run: float accumulators, the run's records in ascending input index (the sorts are stable) — the additions
-// and the division of rs_centroid_kernel (lsd_sort.hip), the records read where they lie.  Run r in key order -> cx/cy/cz/cw[r]; the
-// run of the non-finite records (key == cells, always last) is dropped.
+// Every head sums its run: the walk, the additions and the division of rs_centroid_kernel (lsd_sort.hip; voxel_device.hpp:
+// run_centroid), the records read where they lie.  Run r in key order -> cx/cy/cz/cw[r]; the run of the non-finite records
+// (key == cells, always last) is dropped.
 __global__ __launch_bounds__(256) void mf_centroid_kernel(const unsigned int* __restrict__ lo, const unsigned int* __restrict__ hi,
                                                           const int* __restrict__ order, size_t n, const int* __restrict__ block_base,
                                                           unsigned long long cells, int has_sentinel, const unsigned char* __restrict__ data,
                                                           int step, int ox, int oy, int oz, int oi, float* __restrict__ cx,
                                                           float* __restrict__ cy, float* __restrict__ cz, float* __restrict__ cw) {
-  __shared__ int s_w[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const KeysHiLo K{lo, hi};
   const size_t i = (size_t)blockIdx.x * MF_CHUNK + threadIdx.x;
-  const bool head = (i < n) && mf_is_head(lo, hi, i);
-  const unsigned long long heads = __ballot(head);
-  if (lane == 0) s_w[wave] = __popcll(heads);
-  __syncthreads();
+  const bool head = (i < n) && run_is_head(K, i);
+  const int r = run_rank_in_block(head, block_base);
   if (!head) return;
-  int r = block_base[blockIdx.x] + __popcll(heads & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
-  for (int k = 0; k < wave; k++) r += s_w[k];
-  const unsigned long long key = ((unsigned long long)(hi ? hi[i] : 0u) << 32) | lo[i];
+  const unsigned long long key = K.at(i);
   if (has_sentinel && key == cells) return;
-  float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
-  size_t j = i;
-  // the additions are a chain by definition (float, in index order); the gathers that feed them are not: four records in flight
-  for (; j + 3 < n && mf_same(lo, hi, j + 3, i); j += 4) {   // sorted keys: position j + 3 in the run implies the three before it
-    const unsigned char* r0 = data + (size_t)order[j] * step;
-    const unsigned char* r1 = data + (size_t)order[j + 1] * step;
-    const unsigned char* r2 = data + (size_t)order[j + 2] * step;
-    const unsigned char* r3 = data + (size_t)order[j + 3] * step;
-    const float x0 = mf_field(r0, ox), y0 = mf_field(r0, oy), z0 = mf_field(r0, oz), x1 = mf_field(r1, ox), y1 = mf_field(r1, oy), z1 = mf_field(r1, oz);
-    const float x2 = mf_field(r2, ox), y2 = mf_field(r2, oy), z2 = mf_field(r2, oz), x3 = mf_field(r3, ox), y3 = mf_field(r3, oy), z3 = mf_field(r3, oz);
-    float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
-    if (oi >= 0) { w0 = mf_field(r0, oi); w1 = mf_field(r1, oi); w2 = mf_field(r2, oi); w3 = mf_field(r3, oi); }
-    sx += x0; sy += y0; sz += z0; sx += x1; sy += y1; sz += z1; sx += x2; sy += y2; sz += z2; sx += x3; sy += y3; sz += z3;
-    if (oi >= 0) { sw += w0; sw += w1; sw += w2; sw += w3; }
-  }
-  for (; j < n && mf_same(lo, hi, j, i); j++) {
-    const unsigned char* rec = data + (size_t)order[j] * step;
-    sx += mf_field(rec, ox); sy += mf_field(rec, oy); sz += mf_field(rec, oz);
-    if (oi >= 0) sw += mf_field(rec, oi);
-  }
-  const float m = (float)(j - i);
-  cx[r] = sx / m; cy[r] = sy / m; cz[r] = sz / m;
-  cw[r] = (oi >= 0) ? sw / m : 0.f;
+  float c[4];
+  run_centroid(K, key, RecordPoints{data, step, ox, oy, oz, oi}, order, i, n, c);
+  cx[r] = c[0]; cy[r] = c[1]; cz[r] = c[2]; cw[r] = c[3];
 }
 
 // the output records, one 4-byte word per thread: a field's word takes its plane's value, every other word is zero
@@ -193,12 +123,6 @@ __global__ __launch_bounds__(256) void mf_write_kernel(const float* __restrict__
   else if (w == wz) v = __float_as_uint(cz[r]);
   else if (w == wi) v = __float_as_uint(cw[r]);
   out[t] = v;
-}
-
-int bits_for_u64(unsigned long long v) {   // bits needed to write v (at least 1)
-  int b = 1;
-  while (b < 64 && (v >> b) != 0ull) b++;
-  return b;
 }
 
 int mf_limit_error(const char* what) {
@@ -248,21 +172,21 @@ int map_filter_runs(MapFilterState& S, const void* d_records, size_t n, const Mf
 
   // ---- the grid, and what is beyond it
   const float inv_leaf = 1.0f / leaf;
+  const GridDims G = grid_dims(mn, mx, inv_leaf);
   unsigned long long cells = 1;
   for (int k = 0; k < 3; k++) {
-    const float lo = std::floor(mn[k] * inv_leaf), hi = std::floor(mx[k] * inv_leaf);
-    if (!(std::fabs(lo) < (float)MF_CELL_LIMIT) || !(std::fabs(hi) < (float)MF_CELL_LIMIT))
+    if (!(std::fabs(G.cell_lo[k]) < (float)MF_CELL_LIMIT) || !(std::fabs(G.cell_hi[k]) < (float)MF_CELL_LIMIT))
       return mf_limit_error("map filter: a cell coordinate reaches 2^24 (a float coordinate carries no leaf resolution there): leaf size too small for where the cloud lies");
-    P->min_b[k] = (int)lo;
-    P->div_b[k] = (int)hi - P->min_b[k] + 1;
+    P->min_b[k] = G.min_b[k];
+    P->div_b[k] = G.div_b[k];
     if (P->div_b[k] > MF_DIV_LIMIT)
       return mf_limit_error("map filter: more than 2^21 cells along an axis: leaf size too small for the cloud extent");
     cells *= (unsigned long long)P->div_b[k];
   }
   P->cells = cells;
-  P->index_bits = bits_for_u64(cells - 1);
+  P->index_bits = bits_for(cells - 1);
   const bool has_sentinel = n_finite < (unsigned long long)n;
-  P->sort_bits = has_sentinel ? bits_for_u64(cells) : P->index_bits;
+  P->sort_bits = has_sentinel ? bits_for(cells) : P->index_bits;
   const bool wide = P->sort_bits > 32;
   S.key_bits = P->index_bits;
 
@@ -386,37 +310,48 @@ int mf_check_out(const void* out_data, const lsr_pc2_layout* out_layout) {
   return arg_error(check_records(out_data, 0, MAP_RECORD_LIMIT, true, "out_data"));   // (null: the count alone)
 }
 
-// n records of in_layout in DEVICE memory at d_in -> the filtered records of out_layout at out_data (host or device; null: count only).
-// The arguments have been checked.  *n_out as lsr_voxel_grid_filter_map sets it.
-int mf_filter_device(lsr_handle h, const void* d_in, size_t n, const lsr_pc2_layout* in_layout, float leaf, void* out_data,
-                     size_t capacity_points, const lsr_pc2_layout* out_layout, bool out_on_device, size_t* n_out) {
+// n records of layout F in DEVICE memory at d_in thinned into device memory: the runs, then (unless count_only, or no leaf) the m records
+// of layout O emitted, the stream synchronised and the legs' times collected.  They go to d_out (room for `capacity` records) or,
+// d_out null, into `grow`, reserved to fit; h_out non-null: copied on to host memory in front of the synchronisation.  *m_out: the
+// leaves, set on success and when the buffer is too small.
+int mf_thin(lsr_handle h, const void* d_in, size_t n, const MfFields& F, float leaf, const MfFields& O, bool count_only, void* d_out,
+            size_t capacity, DevBuf<unsigned char>* grow, void* h_out, size_t* m_out) {
   MapFilterState& S = h->map_filter;
   if (n > MF_SORT_LIMIT) { set_last_error("map filter: more than INT32_MAX / 2 records (the sort's limit)"); return LSR_ERR_INDEX_OVERFLOW; }
-  const MfFields F = mf_fields(in_layout), O = mf_fields(out_layout);
   const bool profile = h->profile != 0;
   MfPlan P;
   int st = map_filter_runs(S, d_in, n, F, leaf, h->stream, profile, &P);
   if (st) return st;
   const size_t m = P.n_leaves;
-  if (!out_data || m == 0) {
+  if (count_only || m == 0) {
     if (profile && P.n_finite > 0 && (st = map_filter_collect_ms(S, false))) return st;
-    *n_out = m;
+    *m_out = m;
     return LSR_OK;
   }
-  if (capacity_points < m) {
-    *n_out = m;
+  if (capacity < m) {
+    *m_out = m;
     set_last_error("output buffer too small");
     return LSR_ERR_INVALID_ARGUMENT;
   }
   const size_t out_bytes = m * (size_t)O.step;
-  if (!out_on_device && (st = h->map_out.reserve(out_bytes))) return st;
-  void* d_out = out_on_device ? out_data : static_cast<void*>(h->map_out.p);
+  if (!d_out) {
+    if ((st = grow->reserve(out_bytes))) return st;
+    d_out = grow->p;
+  }
   if ((st = map_filter_emit(S, d_in, F, P, d_out, O, h->stream, profile))) return st;
-  if (!out_on_device) LSR_HIP(hipMemcpyAsync(out_data, h->map_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (h_out) LSR_HIP(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
   LSR_HIP(hipStreamSynchronize(h->stream));
   if (profile && (st = map_filter_collect_ms(S, true))) return st;
-  *n_out = m;
+  *m_out = m;
   return LSR_OK;
+}
+
+// the same for the entries that hand out records: out_data in host or device memory (null: count only).  The arguments have been
+// checked.  *n_out as lsr_voxel_grid_filter_map sets it.
+int mf_filter_device(lsr_handle h, const void* d_in, size_t n, const lsr_pc2_layout* in_layout, float leaf, void* out_data,
+                     size_t capacity_points, const lsr_pc2_layout* out_layout, bool out_on_device, size_t* n_out) {
+  return mf_thin(h, d_in, n, mf_fields(in_layout), leaf, mf_fields(out_layout), !out_data, out_on_device ? out_data : nullptr, capacity_points,
+                 &h->map_out, out_on_device ? nullptr : out_data, n_out);
 }
 
 int mf_count_submaps(const lsr_submap* submaps, int num_submaps, size_t* total_out) {
@@ -502,16 +437,9 @@ int lsr_save_map_pcd_filtered(lsr_handle h, const char* path, const lsr_submap* 
   MapFilterState& S = h->map_filter;
   {
     StreamDrain drain{h->stream};
-    if (n > MF_SORT_LIMIT) { set_last_error("map filter: more than INT32_MAX / 2 records (the sort's limit)"); return LSR_ERR_INDEX_OVERFLOW; }
     const MfFields F = mf_fields(&MF_XYZI);
-    const bool profile = h->profile != 0;
-    MfPlan P;
-    if ((st = map_filter_runs(S, h->pcd.map.p, n, F, leaf, h->stream, profile, &P))) return st;
-    m = P.n_leaves;
+    if ((st = mf_thin(h, h->pcd.map.p, n, F, leaf, F, false, nullptr, SIZE_MAX, &S.thin, nullptr, &m))) return st;
     if (m == 0) { set_last_error("submaps[]: a map without a finite point has no PCD file"); return LSR_ERR_INVALID_ARGUMENT; }
-    if ((st = S.thin.reserve(m * MF_XYZI.point_step)) || (st = map_filter_emit(S, h->pcd.map.p, F, P, S.thin.p, F, h->stream, profile))) return st;
-    LSR_HIP(hipStreamSynchronize(h->stream));
-    if (profile && (st = map_filter_collect_ms(S, true))) return st;
   }
   size_t bytes = 0;
   if ((st = lsr_save_pcd(h, path, S.thin.p, m, &MF_XYZI, 1, data_kind, &bytes))) return st;

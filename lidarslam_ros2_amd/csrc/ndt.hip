@@ -23,6 +23,7 @@
 #include "grid_device.hpp"
 #include "ndt_point.hpp"
 #include "sort.hpp"
+#include "voxel_device.hpp"   // wave_sum
 
 namespace lsr {
 
@@ -146,12 +147,6 @@ void ndt_fill_diag_state(NdtState& st, const double* p6, const float* T16, int c
 // K3 + K4: derivative pass with fused controller
 // ===========================================================================================
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // The controller works on an LDS image of NdtState: typed LDS pointers let the compiler emit ds_read /
 // ds_write instead of flat accesses even though the controller is not inlined into the kernel.

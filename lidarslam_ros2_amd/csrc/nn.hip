@@ -13,6 +13,7 @@
 #include "handle.hpp"
 #include "nn_device.hpp"
 #include "sort.hpp"
+#include "voxel_device.hpp"
 
 namespace lsr {
 
@@ -537,8 +538,7 @@ __global__ __launch_bounds__(256) void assemble_frames_bbox_kernel(const FrameSl
                                                                    size_t stride, float* __restrict__ ox, float* __restrict__ oy,
                                                                    float* __restrict__ oz, unsigned long long* __restrict__ parts_dev,
                                                                    BuildMailbox* __restrict__ mb, unsigned int token) {
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned int cnt = 0;
+  BoxAcc box;
   const int tid = threadIdx.x;
   for (int sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
     int lo = 0, hi = n_frames - 1;   // the last frame whose first slice is <= sl (frames without points own no slice)
@@ -574,36 +574,10 @@ __global__ __launch_bounds__(256) void assemble_frames_bbox_kernel(const FrameSl
       float q[3];
       frame_point_rn(F.T16, p[u][0], p[u][1], p[u][2], q[0], q[1], q[2]);
       ox[out0 + i] = q[0]; oy[out0 + i] = q[1]; oz[out0 + i] = q[2];
-      if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) continue;
-      cnt++;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], q[k]); mx[k] = fmaxf(mx[k], q[k]); }
+      box.add(q[0], q[1], q[2]);
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], m, 64)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], m, 64)); }
-    cnt += __shfl_xor(cnt, m, 64);
-  }
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int wv = tid >> 6;
-  if ((tid & 63) == 0) {
-    for (int k = 0; k < 3; k++) { s_mn[wv][k] = mn[k]; s_mx[wv][k] = mx[k]; }
-    s_cnt[wv] = cnt;
-  }
-  __syncthreads();
-  if (tid < BBOX_GRANULES) {
-    const int k = tid;
-    unsigned int bits;
-    if (k < 3) bits = __float_as_uint(fminf(fminf(s_mn[0][k], s_mn[1][k]), fminf(s_mn[2][k], s_mn[3][k])));
-    else if (k < 6) bits = __float_as_uint(fmaxf(fmaxf(s_mx[0][k - 3], s_mx[1][k - 3]), fmaxf(s_mx[2][k - 3], s_mx[3][k - 3])));
-    else bits = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    const unsigned long long g = ((unsigned long long)token << 32) | bits;
-    parts_dev[(size_t)blockIdx.x * 8 + k] = g;
-    __hip_atomic_store(&mb->part[blockIdx.x].g[k], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  box_publish(box_fold_block(box), &mb->part[blockIdx.x], token, parts_dev + (size_t)blockIdx.x * 8, nullptr);
 }
 
 // ---- N5: the whole map from its submaps — ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of

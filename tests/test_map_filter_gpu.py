@@ -144,6 +144,33 @@ def test_one_point_and_no_finite_point(reg):
     assert empty.shape == (0, 32)
 
 
+def test_a_workgroup_without_a_finite_point_and_a_run_over_the_chunk_seam(reg):
+    """2 049 records: the bounding-box passes of both filters walk them with three workgroups (workgroup b takes the records i with
+    (i mod 768) // 256 == b), the second of which meets nothing but NaN x, so its record is the empty box; the third is partly
+    filled.  The finite records: a leaf of 250 points, then one of 20 — sorted positions 250..269, over the run finder's 256-key
+    seam — then a leaf each.  The int32 filter (twice on a fresh object: grid dimensions on the host, then folded on the device from
+    the ingest's records) and the map filter against the restatement."""
+    rng = np.random.default_rng(305)
+    n = 2049
+    finite = np.flatnonzero((np.arange(n) % 768) // 256 != 1)
+    assert finite.size == 1281
+    cell_x = np.concatenate([np.zeros(250), np.ones(20), 2 + np.arange(finite.size - 270)])
+    rec = np.zeros((n, 8), np.float32)
+    rec[:, 0] = np.nan
+    rec[:, 1:3] = rng.uniform(-5.0, 5.0, (n, 2)).astype(np.float32)     # finite y, z beside the NaN x: the test is on all three
+    rec[finite, :3] = (np.column_stack([cell_x[rng.permutation(finite.size)], np.zeros(finite.size), np.zeros(finite.size)])
+                       + rng.uniform(0.1, 0.9, (finite.size, 3))).astype(np.float32)
+    rec[:, 4] = rng.uniform(0.0, 255.0, n).astype(np.float32)
+    want = mfn.voxel_grid_filter_map(rec, 1.0, XYZI, XYZI)
+    assert want.shape[0] == finite.size - 268
+    fresh = NormalDistributionsTransform(device=0)
+    for _ in range(2):
+        old = fresh.voxelGridFilterPointCloud2(rec.view(np.uint8).reshape(-1), n, 32, XYZI[1], 1.0, 32, XYZI[1])
+        assert np.array_equal(old.reshape(-1, 32), want.view(np.uint8).reshape(-1, 32))
+    for src in (rec, _cuda(rec)):
+        assert np.array_equal(_host(reg.voxelGridFilterMap(src, 1.0)).view(np.uint8).reshape(-1, 32), want.view(np.uint8).reshape(-1, 32))
+
+
 def test_records_behind_two_gib(reg):
     """2^26 + 4096 records of 32 bytes: the byte offset of the last 4 096 passes 2^31, and they are the only finite ones (the records
     in front have a NaN x and are dropped), so the bounding box, the keys and the centroids all come from behind that offset.  The

@@ -307,3 +307,88 @@ def test_uniform_cloud_is_bit_identical_to_the_oracle(O):
     ref = O.voxel_grid_filter(pts, 0.25)
     assert got.shape == ref.shape
     assert np.array_equal(got, ref)
+
+
+# ---- a workgroup of the bounding-box pass that meets no finite point: its record is the empty box {+inf, -inf, 0} -------------------
+def _cloud_with_an_all_nan_workgroup(seed):
+    """2 049 points well away from the origin (a record of zeros in place of the empty box would move min_b / max_b).  The passes
+    walk them with three workgroups, workgroup b taking the points i with (i mod 768) // 256 == b: all of workgroup 1's have a NaN
+    x, workgroup 2 is partly filled (its third trip holds one point)."""
+    rng = np.random.default_rng(seed)
+    pts = (rng.uniform([100.0, -140.0, 30.0], [140.0, -100.0, 34.0], (2049, 3))).astype(np.float32)
+    pts[(np.arange(2049) % 768) // 256 == 1, 0] = np.nan
+    return pts
+
+
+def _assert_grid_is_the_oracles(O, r, pts, res):
+    info, ref = r.gridInfo(), O.VoxelGridCovariance(pts, res)
+    assert np.array_equal(info["min_b"], ref.min_b) and np.array_equal(info["max_b"], ref.max_b)
+    assert info["n_leaves"] == ref.n_leaves and info["n_valid"] == ref.n_valid
+    d, want = r.gridDump(), ref.dump()
+    assert np.array_equal(d["idx"], want["idx"]) and np.array_equal(d["n"], want["n"])    # voxel set and counts: integer work
+    assert np.abs(d["mean"] - want["mean"]).max() < 1e-9                                  # fp64 sums in another order
+
+
+@pytest.mark.parametrize("builder", [0, 1], ids=["counting_sort", "radix_sort"])
+def test_target_with_an_all_nan_workgroup_single(O, builder):
+    """setInputTarget of one cloud: bbox_kernel over the planes, the host folds its three records."""
+    from lidarslam_ros2_amd import NormalDistributionsTransform
+
+    pts = _cloud_with_an_all_nan_workgroup(41)
+    r = NormalDistributionsTransform(device=0)
+    r.setResolution(2.0)
+    if builder:
+        r.setTuning(grid_builder=1)
+    r.setInputTarget(synth.as_pointxyzi(pts))
+    _assert_grid_is_the_oracles(O, r, pts, 2.0)
+
+
+def test_targets_with_an_all_nan_workgroup_as_a_set(O):
+    """lsr_set_input_target_batch: the grouped ingest (vg_ingest_group_kernel) reads the records and leaves three bounding-box records
+    per member; a member without the NaN block rides along."""
+    from lidarslam_ros2_amd import NormalDistributionsTransform
+    from lidarslam_ros2_amd.registration import set_input_target_batch
+
+    plain = np.random.default_rng(43).uniform([100.0, -140.0, 30.0], [140.0, -100.0, 34.0], (2049, 3)).astype(np.float32)
+    clouds = [_cloud_with_an_all_nan_workgroup(42), plain]
+    regs = [NormalDistributionsTransform(device=0) for _ in clouds]
+    for r in regs:
+        r.setResolution(2.0)
+    set_input_target_batch(regs, [synth.as_pointxyzi(c) for c in clouds])
+    for r, c in zip(regs, clouds):
+        _assert_grid_is_the_oracles(O, r, c, 2.0)
+
+
+def test_filtered_frames_with_an_all_nan_slice(O):
+    """lsr_set_input_target_frames_filtered: the one-launch assembly walks 1 024-point slices, a workgroup each — a frame of 1 025
+    points (the second slice holds one) and a frame of 1 024 points with a NaN x, whose workgroup leaves the empty box in the host
+    mailbox (first call: the host folds the records) and in device memory (second call: the key kernel folds them).  The target is
+    the one the oracle's filter of the host-assembled cloud gives: same leaves, bit-identical sums."""
+    import os
+    from lidarslam_ros2_amd import NormalDistributionsTransform
+
+    rng = np.random.default_rng(44)
+    lo, hi = [100.0, -140.0, 30.0], [140.0, -100.0, 34.0]
+    frames = [rng.uniform(lo, hi, (1025, 3)).astype(np.float32), rng.uniform(lo, hi, (1024, 3)).astype(np.float32)]
+    frames[1][:, 0] = np.nan
+    poses = []
+    for yaw, t in ((0.3, (5.0, -3.0, 0.5)), (-0.2, (1.0, 2.0, -0.25))):
+        T = np.eye(4, dtype=np.float32)
+        T[:2, :2] = [[np.cos(yaw), -np.sin(yaw)], [np.sin(yaw), np.cos(yaw)]]
+        T[:3, 3] = t
+        poses.append(T)
+    assembled = np.concatenate([O.transform_point_cloud(f, T) for f, T in zip(frames, poses)])
+    want = O.voxel_grid_filter(assembled, 0.5)
+    assert 0 < want.shape[0] <= 1025
+    a, b = NormalDistributionsTransform(device=0), NormalDistributionsTransform(device=0)
+    for r in (a, b):
+        r.setResolution(2.0)
+    b.setInputTarget(want)
+    db = b.gridDump()
+    for call in range(2):
+        assert a.setInputTargetFramesFiltered([synth.as_pointxyzi(f) for f in frames], poses, 0.5) == want.shape[0]
+        if call == 1 and os.environ.get("LSR_VG_DEVICE_DIMS", "") != "0":
+            assert a.voxelFilterForm() == 2
+        da = a.gridDump()
+        assert np.array_equal(da["idx"], db["idx"]) and np.array_equal(da["n"], db["n"])
+        assert np.array_equal(da["mean"], db["mean"]) and np.array_equal(da["icov"], db["icov"])   # bit-identical target clouds
