@@ -99,8 +99,12 @@ typedef enum lsr_key {
   LSR_MAP_FILTER_RUNS_MS = 19,        /* the run finder and its scan; */
   LSR_MAP_FILTER_CENTROID_MS = 20,    /* the centroids; */
   LSR_MAP_FILTER_WRITE_MS = 21,       /* the write of the output records.  Else 0 (the last two also after a call that only counted) */
+  LSR_MAP_WINDOW_MS = 22,             /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the three launches (count,
+                                         scan, write; copies outside the brackets) of the last lsr_crop_map /
+                                         lsr_set_input_target_window on this object; else 0 (the write is absent after a call that only
+                                         counted or kept nothing) */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
-  LSR_MAX_ITERATIONS = 32,            /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
+  LSR_MAX_ITERATIONS = 32,           /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
   LSR_NUM_THREADS = 34,               /* setNumThreads (accepted, ignored)  scanmatcher_component.cpp:111 */
   LSR_K_CORRESPONDENCES = 35,         /* GICP k_correspondences_ (20) */
@@ -697,6 +701,52 @@ int lsr_assemble_map_filtered(lsr_handle h, const lsr_submap* submaps, int num_s
 int lsr_save_map_pcd_filtered(lsr_handle h, const char* path, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout,
                               int on_device, const double* poses16 /* nullable */, float leaf, int data_kind,
                               size_t* n_points /* nullable */, size_t* n_bytes);
+
+/* ---- localising in a saved map: the target cut from the resident map ------------------------- */
+/* A saved map is far larger than what one scan can meet, and setInputTarget lays one int32 cell table over the bounding box of whatever
+ * it is given (a 6 km x 6 km x 600 m map at resolution 1.0 is LSR_ERR_INDEX_OVERFLOW).  These entries cut the records inside a box of
+ * voxel cells around the pose out of the resident map, in input order, on the device, and build the ordinary target from them.
+ * The definition (csrc/map_window.hip; the predicate: csrc/voxel_device.hpp in_window), all arithmetic in fp32:
+ *   A window is a leaf size and, per axis k, an inclusive range lo[k] .. hi[k] of ABSOLUTE cells of the lattice anchored at the origin.
+ *   inv_leaf = 1.0f / leaf.  For a record with the coordinates p[0..2], f[k] = floorf(p[k] * inv_leaf) — one multiply, then the floor; no
+ *   FMA can form.  The record is KEPT iff p[0], p[1], p[2] are all finite and (float)lo[k] <= f[k] && f[k] <= (float)hi[k] for k = 0, 1, 2.
+ *   The comparison is made in float; nothing is converted to an integer (an f beyond the int range, +-inf included, is simply outside).
+ *   Requirements: leaf > 0 (NaN refused), lo[k] <= hi[k], |lo[k]| < 2^24 and |hi[k]| < 2^24 (there (float) of a cell is exact); anything
+ *   else is LSR_ERR_INVALID_ARGUMENT.  Inside that limit f[k] is, exactly, the absolute cell the voxel grids here assign the point:
+ *   VoxelGrid / VoxelGridCovariance compute (int)(floorf(p[k] * inv_leaf) - (float)min_b[k]) with the same inv_leaf, an integer shift of f.
+ *   Output: the kept records in ascending input index.  Of each, x, y, z and intensity are copied bit for bit from in_layout's offsets to
+ *   out_layout's; an input layout without intensity yields intensity +0, an output layout without intensity has no such field.  Every
+ *   other byte of an output record is zero.
+ *   Consequence: with leaf = the NDT resolution, the target built from the cut holds in every cell of the window exactly the points, in
+ *   the same order, that a target built from the whole map holds there: the leaves have the same bits, and so has every registration
+ *   whose lookups stay inside the window (DIRECT7 / DIRECT1 / DIRECT26; not KDTREE, and not GICP, whose neighbours at the border differ).
+ * lsr_map_window_around (host only, no handle): lo[k] = (int32)floorf((float)(center[k] - half_extent[k]) * inv_leaf), hi[k] likewise with
+ * +; the difference and the sum in double, ONE conversion to float, then the multiply and the floor of the predicate.  Null pointers, a
+ * leaf that is not > 0, a centre or half extent that is not finite, a negative half extent: LSR_ERR_INVALID_ARGUMENT; a |lo[k]| or |hi[k]|
+ * of 2^24 or more: LSR_ERR_INDEX_OVERFLOW.  No error touches *w. */
+typedef struct lsr_map_window { float leaf; int32_t lo[3], hi[3]; } lsr_map_window;   /* inclusive absolute cells */
+int lsr_map_window_around(const double center[3], const double half_extent[3], float leaf, lsr_map_window* w);
+/* n_points records of in_layout at `data` (host, or HIP device pointer with on_device != 0) -> the kept records, of out_layout, at
+ * out_data (host, or HIP device buffer with out_on_device != 0) of capacity_points records; *n_out = how many were kept.  The contract of
+ * lsr_voxel_grid_filter_map: out_data == NULL only counts (capacity_points is ignored); capacity_points below the count is
+ * LSR_ERR_INVALID_ARGUMENT with *n_out set to the count and out_data untouched; an output range that overlaps the input records is
+ * LSR_ERR_INVALID_ARGUMENT; nothing kept (n_points == 0 too) is LSR_OK with *n_out = 0.  Layout, alignment, staging and stream-ordering
+ * rules: those of lsr_assemble_map.  At most INT32_MAX records (LSR_ERR_INDEX_OVERFLOW beyond); byte offsets are size_t throughout.
+ * Every other error leaves all outputs untouched.  Three launches on the object's stream, and no workgroup waits for another: the kept
+ * records counted per workgroup of 256; the counts scanned by one workgroup of 1024 threads; the records written, each ranked among its
+ * workgroup's kept ones by the same predicate.  One host wait, for the count, which sizes the output.  Two forms with the same bytes, as
+ * in lsr_assemble_map: 16-byte loads and stores when both layouts are {32; 0, 4, 8, 16} and both bases 16-byte aligned, field by field
+ * otherwise.  The bytes do not depend on where the buffers live and are identical from call to call.  What the object otherwise
+ * answers (target, source, final transformation, fitness) is unchanged.  LSR_MAP_WINDOW_MS reports the launches' time. */
+int lsr_crop_map(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* in_layout, int on_device,
+                 const lsr_map_window* w, void* out_data, size_t capacity_points, const lsr_pc2_layout* out_layout,
+                 int out_on_device, size_t* n_out);
+/* setInputTarget from a window of the map: lsr_crop_map into a device buffer of pcl::PointXYZI records {32; 0, 4, 8, 16} kept on the
+ * object, then lsr_set_input_target_device over that buffer — the same target, bit for bit, as those two calls made by hand.  *n_kept =
+ * the records kept.  A window that keeps nothing is LSR_ERR_INVALID_ARGUMENT with *n_kept = 0, and the previous target stays.  One host
+ * wait in front of the target build: for the count. */
+int lsr_set_input_target_window(lsr_handle h, const void* data, size_t n_points, const lsr_pc2_layout* in_layout,
+                                int on_device, const lsr_map_window* w, size_t* n_kept);
 
 /* ---- reading .pcd files (the other half of map.pcd) ------------------------------------------ */
 /* PCD v0.7 files, DATA ascii, DATA binary and (with LSR_PCD_READ_COMPRESSED = 1) DATA binary_compressed, decoded on the device into records of an lsr_pc2_layout.  The semantics are RESTATED from

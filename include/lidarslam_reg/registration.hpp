@@ -132,6 +132,19 @@ class Registration {
     lsr_odom_guess(sim_trans.data(), previous_odom.data(), odom.data(), guess.data());
     return guess;
   }
+  // ---- localising in a saved map ----
+  // setInputTarget from the window `w` (lsr_map_window_around; map_window.hpp: MapWindowTracker) of a resident map: n_points records
+  // of `layout`, host or device.  The cut is made on the device; the object keeps it, not the caller's cloud.  false: refused (a window
+  // that keeps nothing included), the previous target stays.
+  bool setInputTargetWindow(const void* map_records, size_t n_points, const lsr_pc2_layout& layout, const lsr_map_window& w,
+                            bool on_device = true, size_t* n_kept = nullptr) {
+    size_t kept = 0;
+    const int st = lsr_set_input_target_window(h_, map_records, n_points, &layout, on_device ? 1 : 0, &w, &kept);
+    check(st, "setInputTargetWindow");
+    if (st == LSR_OK) target_.reset();
+    if (n_kept) *n_kept = kept;
+    return st == LSR_OK;
+  }
   const lsr_result& lastResult() const { return last_; }
   lsr_handle handle() const { return h_; }
 

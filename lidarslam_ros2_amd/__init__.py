@@ -4,12 +4,14 @@ Only the `pcl::Registration` path (NDT / GICP setInputTarget, setInputSource, al
 getFitnessScore) is implemented here — hand-written HIP kernels for gfx950 behind the C ABI in
 include/lidarslam_reg.h.  See DESIGN.md.
 """
-from .registration import (DIRECT1, DIRECT7, DIRECT26, KDTREE, GeneralizedIterativeClosestPoint,
-                           NormalDistributionsTransform, Registration, align_batch, odomGuess, sensorTransformMatrix)
+from .registration import (DIRECT1, DIRECT7, DIRECT26, KDTREE, GeneralizedIterativeClosestPoint, MapWindow,
+                           NormalDistributionsTransform, Registration, align_batch, mapWindowAround, odomGuess, sensorTransformMatrix)
 from .loop_closure import LoopClosureParams, LoopEdge, SubMap, search_loop
 from .map_array import MapArray
+from .localization import Localizer, LocalizerParams
 from . import pose_graph
 
 __all__ = ["Registration", "NormalDistributionsTransform", "GeneralizedIterativeClosestPoint", "align_batch",
            "odomGuess", "sensorTransformMatrix", "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray", "pose_graph",
+           "MapWindow", "mapWindowAround", "Localizer", "LocalizerParams",
            "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]

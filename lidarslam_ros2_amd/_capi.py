@@ -28,6 +28,8 @@ PCD_DEFLATE_MS = 15
 (MAP_FILTER_BBOX_MS, MAP_FILTER_KEY_MS, MAP_FILTER_SORT_MS, MAP_FILTER_RUNS_MS, MAP_FILTER_CENTROID_MS,
  MAP_FILTER_WRITE_MS) = range(16, 22)
 MAP_FILTER_KEY_BITS = 55
+MAP_WINDOW_MS = 22
+MAP_WINDOW_CELL_LIMIT = 1 << 24
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2           # lsr_pcd_data
 PCD_DATA_KINDS = {"ascii": PCD_ASCII, "binary": PCD_BINARY, "binary_compressed": PCD_BINARY_COMPRESSED}
 PCD_LZF_CHUNK_BYTES = 4096
@@ -59,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "lsr_parse_pcd_header", "lsr_decode_pcd", "lsr_load_pcd", "lsr_set_input_target_pcd",
     "lsr_format_pcd", "lsr_save_pcd", "lsr_save_map_pcd", "lsr_lzf_deflate",
     "lsr_voxel_grid_filter_map", "lsr_assemble_map_filtered", "lsr_save_map_pcd_filtered",
+    "lsr_map_window_around", "lsr_crop_map", "lsr_set_input_target_window",
 ]
 
 
@@ -109,6 +112,10 @@ class PoseGraphTrace(C.Structure):
 class Pc2Layout(C.Structure):
     _fields_ = [("point_step", C.c_uint32), ("offset_x", C.c_uint32), ("offset_y", C.c_uint32), ("offset_z", C.c_uint32),
                 ("offset_intensity", C.c_int32)]
+
+
+class MapWindow(C.Structure):
+    _fields_ = [("leaf", C.c_float), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
 
 
 class PcdInfo(C.Structure):
@@ -203,6 +210,10 @@ def load() -> C.CDLL:
                                             C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_save_map_pcd_filtered.argtypes = [vp, C.c_char_p, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, C.c_float, C.c_int,
                                             C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.lsr_map_window_around.argtypes = [dp, dp, C.c_float, C.POINTER(MapWindow)]
+    L.lsr_crop_map.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(MapWindow), vp, C.c_size_t, C.POINTER(Pc2Layout),
+                               C.c_int, C.POINTER(C.c_size_t)]
+    L.lsr_set_input_target_window.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(MapWindow), C.POINTER(C.c_size_t)]
     L.lsr_parse_pcd_header.argtypes = [vp, C.c_size_t, C.POINTER(PcdInfo)]
     L.lsr_decode_pcd.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_load_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]

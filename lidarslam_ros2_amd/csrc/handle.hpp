@@ -4,6 +4,7 @@
 #include "deskew.hpp"
 #include "gicp.hpp"
 #include "map_filter.hpp"
+#include "map_window.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
 #include "pcd_deflate.hpp"
@@ -104,6 +105,8 @@ struct lsr_handle_s {
   lsr::PcdReadState pcd_read;  // lsr_decode_pcd / lsr_load_pcd / lsr_set_input_target_pcd (csrc/pcd_read.hip): buffers, kept between calls
 
   lsr::MapFilterState map_filter;   // lsr_voxel_grid_filter_map / lsr_assemble_map_filtered / lsr_save_map_pcd_filtered (csrc/map_filter.hip): scratch, kept between calls
+
+  lsr::MapWindowState map_window;   // lsr_crop_map / lsr_set_input_target_window (csrc/map_window.hip): scratch, kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1): one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

@@ -96,6 +96,21 @@ inline ArgStatus check_records_in_out(const void* data, const void* out_data, si
   return check_in_place_or_disjoint(data, out_data, n * step);
 }
 
+// ---- map windows -----------------------------------------------------------------------------------------------------------------
+// a leaf size > 0 (NaN refused) and, per axis, lo <= hi with both cells below 2^24 in magnitude ((float) of a cell is exact there)
+constexpr int64_t WINDOW_CELL_LIMIT = (int64_t)1 << 24;
+inline ArgStatus check_window_arg(const lsr_map_window* w, const char* what = "window") {
+  if (!w) return arg_invalid(what, "null map window");
+  if (!(w->leaf > 0)) return arg_invalid(what, "the leaf size must be > 0");
+  for (int k = 0; k < 3; k++) {
+    if (w->lo[k] > w->hi[k]) return arg_invalid(what, "lo[k] > hi[k]");
+    const int64_t lo = w->lo[k], hi = w->hi[k];
+    if (lo <= -WINDOW_CELL_LIMIT || lo >= WINDOW_CELL_LIMIT || hi <= -WINDOW_CELL_LIMIT || hi >= WINDOW_CELL_LIMIT)
+      return arg_invalid(what, "a cell of 2^24 or beyond (a float coordinate carries no leaf resolution there)");
+  }
+  return arg_ok();
+}
+
 // ---- frame lists -----------------------------------------------------------------------------------------------------------------
 // n_frames clouds of one stride with a pose each (lsr_set_input_target_frames and what shares its assembly); -> the records in all and
 // in the biggest frame

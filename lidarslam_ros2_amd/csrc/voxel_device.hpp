@@ -100,6 +100,18 @@ __device__ __forceinline__ int leaf_axis(float pk, float inv_leaf, int min_b) { 
 __device__ __forceinline__ LeafCell leaf_cell(float px, float py, float pz, float inv_leaf, int mb0, int mb1, int mb2) {
   return LeafCell{leaf_axis(px, inv_leaf, mb0), leaf_axis(py, inv_leaf, mb1), leaf_axis(pz, inv_leaf, mb2)};
 }
+// The map window (include/lidarslam_reg.h: lsr_map_window): a point is inside iff it is finite and its ABSOLUTE cell
+// floorf(p * inv_leaf) — the float leaf_axis forms before it subtracts min_b — lies in [lo, hi] on every axis.  The bounds are the
+// window's int cells as floats (exact below 2^24); the comparison stays in float: no conversion, and no min_b to subtract.
+struct WindowCells { float lo[3], hi[3]; };
+__device__ __forceinline__ bool window_axis(float pk, float inv_leaf, float lo, float hi) {
+  const float f = floorf(pk * inv_leaf);
+  return lo <= f && f <= hi;
+}
+__device__ __forceinline__ bool in_window(float px, float py, float pz, float inv_leaf, const WindowCells& W) {
+  return point_finite(px, py, pz) && window_axis(px, inv_leaf, W.lo[0], W.hi[0]) && window_axis(py, inv_leaf, W.lo[1], W.hi[1]) &&
+         window_axis(pz, inv_leaf, W.lo[2], W.hi[2]);
+}
 // i0 + i1 * div_b[0] + i2 * div_b[0] * div_b[1], the products in T (int: the int32 filters and builders; long long: the map filter)
 template <class T>
 __device__ __forceinline__ T leaf_index(const LeafCell& c, T mul1, T mul2) { return (T)c.i0 + (T)c.i1 * mul1 + (T)c.i2 * mul2; }
@@ -154,20 +166,23 @@ struct KeysHiLo {   // (high, low) words; hi == null: the low word is the whole 
 template <class Keys, class I>
 __device__ __forceinline__ bool run_is_head(const Keys& K, I i) { return i == 0 || !K.is(i, K.at(i - 1)); }
 
-// The heads among this workgroup's 256 positions (valid in thread 0).  Called by all threads: one barrier inside.
-template <class Keys, class I>
-__device__ __forceinline__ int run_heads_in_block(const Keys& K, I i, I n) {
+// The threads of a workgroup of 256 whose flag is set, counted.  Called by all threads: one barrier inside.
+__device__ __forceinline__ int flags_in_block(bool flag) {
   __shared__ int s_w[4];
-  int c = (i < n && run_is_head(K, i)) ? 1 : 0;
+  int c = flag ? 1 : 0;
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
   __syncthreads();
   return s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
+// The heads among this workgroup's 256 positions.
+template <class Keys, class I>
+__device__ __forceinline__ int run_heads_in_block(const Keys& K, I i, I n) { return flags_in_block(i < n && run_is_head(K, i)); }
 
 // The number of heads in front of this thread's position: those of the workgroups before (block_base[blockIdx.x]), of the earlier
-// waves and of the lanes below.  For a head that is the index of its run.  Called by all threads: one barrier inside.
+// waves and of the lanes below.  For a head that is the index of its run.  Called by all threads: one barrier inside.  (The flag need
+// not be a run's head: the map window ranks the records it keeps with it.)
 __device__ __forceinline__ int run_rank_in_block(bool head, const int* __restrict__ block_base) {
   __shared__ int s_w[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

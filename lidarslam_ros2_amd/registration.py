@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -22,6 +22,33 @@ from . import _capi as capi
 
 DIRECT7, DIRECT1, DIRECT26, KDTREE = capi.DIRECT7, capi.DIRECT1, capi.DIRECT26, capi.KDTREE
 PC2_XYZI = (32, (0, 4, 8, 16))   # pcl::PointXYZI as pcl::toROSMsg lays it out: (point_step, (x, y, z, intensity or None))
+
+
+class MapWindow(NamedTuple):
+    """lsr_map_window: a leaf size and, per axis, the inclusive range lo .. hi of absolute voxel cells (cell = floor(p / leaf))."""
+    leaf: float
+    lo: Tuple[int, int, int]
+    hi: Tuple[int, int, int]
+
+    def contains(self, p) -> bool:
+        """Whether the point p (fp32 arithmetic, the cut's own predicate) lies in the window."""
+        f = np.floor(np.asarray(p, np.float32)[:3] * (np.float32(1.0) / np.float32(self.leaf)))
+        return bool(np.all((np.asarray(self.lo, np.float32) <= f) & (f <= np.asarray(self.hi, np.float32))))
+
+
+def mapWindowAround(center, half_extent, leaf: float) -> MapWindow:
+    """The window of whole cells of size `leaf` that covers center +- half_extent (metres, per axis) through lsr_map_window_around;
+    needs no device.  A cell of 2^24 or beyond raises (LSR_ERR_INDEX_OVERFLOW)."""
+    c = (C.c_double * 3)(*[float(v) for v in center])
+    e = (C.c_double * 3)(*[float(v) for v in half_extent])
+    w = capi.MapWindow()
+    capi.check(capi.load().lsr_map_window_around(c, e, C.c_float(leaf), C.byref(w)), "mapWindowAround")
+    return MapWindow(float(w.leaf), tuple(int(v) for v in w.lo), tuple(int(v) for v in w.hi))
+
+
+def _window_struct(window) -> capi.MapWindow:
+    leaf, lo, hi = window
+    return capi.MapWindow(float(leaf), (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]))
 
 
 def _is_torch_cuda(x) -> bool:
@@ -524,6 +551,51 @@ class Registration:
         capi.check(self._lib.lsr_voxel_grid_filter_map(self._h, ptr, n, C.byref(li), 1 if dev else 0, C.c_float(leaf), C.c_void_p(optr), cap,
                                                        C.byref(lo), 1 if out_dev else 0, C.byref(n_out)), "voxelGridFilterMap")
         return self._trimmed(flat, int(n_out.value), out_step, cap, own)
+
+    def cropMap(self, records, window, layout=PC2_XYZI, out_layout=PC2_XYZI, out=None):
+        """The records of a map whose absolute voxel cell lies in `window` (MapWindow, or (leaf, lo, hi)), in input order, through
+        lsr_crop_map: x, y, z and intensity moved from `layout` to `out_layout`, every other byte zero.  `records`: numpy array (->
+        uint8 numpy array) or CUDA tensor (-> uint8 CUDA tensor, nothing leaves HBM).  `out`: None = the records are counted first and a
+        buffer of that size is allocated; else the uint8 buffer to write.  -> (m, out point_step) uint8."""
+        li, lo, w = self._layout(*layout), self._layout(*out_layout), _window_struct(window)
+        out_step = int(out_layout[0])
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
+        n_out = C.c_size_t()
+        own = out is None
+        if own:
+            capi.check(self._lib.lsr_crop_map(self._h, ptr, n, C.byref(li), 1 if dev else 0, C.byref(w), None, 0, C.byref(lo), 0,
+                                              C.byref(n_out)), "cropMap")
+        _, flat, optr, cap, out_dev = self._out_records(out, out_step, int(n_out.value), dev)
+        capi.check(self._lib.lsr_crop_map(self._h, ptr, n, C.byref(li), 1 if dev else 0, C.byref(w), C.c_void_p(optr), cap, C.byref(lo),
+                                          1 if out_dev else 0, C.byref(n_out)), "cropMap")
+        return self._trimmed(flat, int(n_out.value), out_step, cap, own)
+
+    def countMapWindow(self, records, window, layout=PC2_XYZI) -> int:
+        """How many records cropMap would keep (lsr_crop_map without an output buffer)."""
+        li, lo, w = self._layout(*layout), self._layout(*PC2_XYZI), _window_struct(window)
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
+        n_out = C.c_size_t()
+        capi.check(self._lib.lsr_crop_map(self._h, ptr, n, C.byref(li), 1 if dev else 0, C.byref(w), None, 0, C.byref(lo), 0,
+                                          C.byref(n_out)), "countMapWindow")
+        return int(n_out.value)
+
+    def setInputTargetWindow(self, records, window, layout=PC2_XYZI) -> int:
+        """setInputTarget from the window of a resident map (lsr_set_input_target_window): cropMap into a buffer kept on the object,
+        then setInputTarget over it, the same target bit for bit.  Returns the number of target points; a window that keeps none
+        raises and the previous target stays."""
+        li, w = self._layout(*layout), _window_struct(window)
+        ptr, n, dev, keep = _payload_args(self, records, int(layout[0]))
+        n_kept = C.c_size_t()
+        capi.check(self._lib.lsr_set_input_target_window(self._h, ptr, n, C.byref(li), 1 if dev else 0, C.byref(w), C.byref(n_kept)),
+                   "setInputTargetWindow")
+        self._n_target = int(n_kept.value)
+        self._keep["target"] = None
+        return self._n_target
+
+    def mapWindowMs(self) -> float:
+        """hipEvent time [ms] of the three launches of the last cropMap / setInputTargetWindow on this object (LSR_MAP_WINDOW_MS; needs
+        LSR_PROFILE = 1, else 0)."""
+        return self._getf(capi.MAP_WINDOW_MS)
 
     def mapFilterKeyBits(self) -> int:
         """The bits of the largest leaf index of the last map filter on this object (LSR_MAP_FILTER_KEY_BITS); above 32 the index was
