@@ -103,6 +103,9 @@ typedef enum lsr_key {
                                          scan, write; copies outside the brackets) of the last lsr_crop_map /
                                          lsr_set_input_target_window on this object; else 0 (the write is absent after a call that only
                                          counted or kept nothing) */
+  LSR_POSE_SEARCH_MS = 23,            /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the scoring launch (the
+                                         pose upload and the copy of the scores outside the brackets) of the last lsr_ndt_score_poses /
+                                         lsr_ndt_search_pose on this object; else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,           /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -903,6 +906,55 @@ int lsr_ndt_derivatives(lsr_handle h, const double* p6, const float* T16, int co
 /* The same; pairs (nullable) receives the number of valid (point, voxel) pairs of the pass. */
 int lsr_ndt_derivatives_pairs(lsr_handle h, const double* p6, const float* T16, int compute_hessian, double* score,
                               double* grad, double* hess, double* pairs);
+
+/* ---- NDT pose search: score the source over a lattice of poses, refine the distinct best ------------------------------------
+ * For an object that has a target and a source but no guess inside NDT's basin of convergence (a vehicle switched on somewhere in a
+ * saved map).  No reference site exists — the reference's answer is a person clicking `initial_pose` in rviz —: the definitions
+ * below are this project's (unpinned).
+ *
+ * lsr_ndt_score_poses: poses16 = count column-major 4x4 float transforms on the host, in the form of lsr_align's guess;
+ * 1 <= count <= LSR_POSE_SEARCH_MAX_POSES.  score[c] and pairs[c] (pairs nullable) are exactly the score and pairs that
+ * lsr_ndt_derivatives_pairs(h, p, &poses16[16 c], 0, ...) returns for this target, source, resolution, outlier ratio and
+ * neighbourhood, bit for bit (the score of a pass with T16 given does not depend on p) — all poses in ONE launch.  DIRECT7, DIRECT1
+ * and DIRECT26, in the table mode the object's derivative passes use; KDTREE is LSR_ERR_NOT_IMPLEMENTED.  Without a target or a
+ * source the call fails as lsr_ndt_derivatives does.  LSR_ERR_INVALID_ARGUMENT, outputs untouched: null handle, poses16 or score;
+ * count == 0 or above the limit; a pose entry that is not finite.  What the object otherwise answers (target, source, final
+ * transformation, converged, fitness) is unchanged.  LSR_POSE_SEARCH_MS reports the launch's time. */
+#define LSR_POSE_SEARCH_MAX_POSES (1 << 20)
+#define LSR_POSE_SEARCH_MAX_KEPT 16
+int lsr_ndt_score_poses(lsr_handle h, const float* poses16, size_t count, double* score, double* pairs /* nullable */);
+
+/* A lattice of poses around a centre: n[0] x n[1] x n[2] translations, `step` apart per axis, times n_yaw headings, yaw_step apart,
+ * all centred.  Candidate c = ((m n[2] + k) n[1] + j) n[0] + i has the offsets (i - (n[0] - 1) / 2.0) step[0], (j - ...) step[1],
+ * (k - ...) step[2] and the heading psi = (m - (n_yaw - 1) / 2.0) yaw_step: R_c = Rz(psi) R_center, t_c = t_center + offsets, in
+ * double from the float centre with the C library's cos and sin; each of the 12 entries is rounded to float once, the last row is
+ * 0 0 0 1.  Host only, no handle.  *count = the number of poses; poses16 == NULL only counts; capacity (in poses) below the count:
+ * LSR_ERR_INVALID_ARGUMENT with *count set.  An n below 1, a product above LSR_POSE_SEARCH_MAX_POSES, a step or a centre entry
+ * that is not finite, a null centre, lattice or count: LSR_ERR_INVALID_ARGUMENT. */
+typedef struct lsr_pose_lattice { int32_t n[3]; double step[3]; int32_t n_yaw; double yaw_step; } lsr_pose_lattice;
+int lsr_pose_lattice_poses(const float* center16, const lsr_pose_lattice* L, float* poses16, size_t capacity, size_t* count);
+
+/* The distinct best of a scored list: the candidates in order of descending score (ties: ascending index; a score that is NaN or not
+ * > 0 is never kept) are walked greedily, and one that is close to an already kept one is skipped.  Close: the translation distance
+ * (double, sqrt(dx dx + dy dy + dz dz)) is < min_sep_m AND (trace(R_a^T R_b) - 1) / 2 > cos(min_sep_rad).  Stops at top_k kept,
+ * 1 <= top_k <= LSR_POSE_SEARCH_MAX_KEPT.  kept[0 .. *n_kept) = their indices, best first.  Host only, sequential on purpose. */
+int lsr_select_poses(const double* score, const float* poses16, size_t count, int top_k, double min_sep_m, double min_sep_rad,
+                     int32_t* kept, int* n_kept);
+
+/* The whole search: the lattice around center16, its scores, the selection; then every kept candidate is refined by the object's
+ * own NDT schedule, all of them as ONE candidate set (worker objects on the object's stream that share its target and hold a copy
+ * of its source, as lsr_search_loop(top_k > 1) keeps them) — a refined pose has the bits lsr_align(h, candidate) gives alone.  The
+ * winner is the largest refined[e].score (trans_probability), ties to the lower rank; best16 and *result receive the winner's and
+ * become the object's final transformation and converged flag, as after lsr_align.  Nothing kept: LSR_OK with n_kept = 0,
+ * winner = -1, best16 untouched and result->converged = 0.  report (nullable): kept[e], coarse_score[e], refined16[16 e ..] and
+ * refined[e] per kept candidate e, best coarse score first.  Errors of the three entries above; a GICP object and a top_k outside
+ * 1 .. 16 are LSR_ERR_INVALID_ARGUMENT. */
+typedef struct lsr_pose_search_params { lsr_pose_lattice lattice; int32_t top_k; double min_sep_m, min_sep_rad; } lsr_pose_search_params;
+typedef struct lsr_pose_search_report { int32_t n_candidates, n_kept, winner; int32_t kept[16]; double coarse_score[16];
+                                        float refined16[16 * 16]; lsr_result refined[16]; } lsr_pose_search_report;
+int lsr_ndt_search_pose(lsr_handle h, const float* center16, const lsr_pose_search_params* p, float* best16, lsr_result* result,
+                        lsr_pose_search_report* report /* nullable */);
+
 /* GICP per-point covariances after setInput*: which = 0 source, 1 target (regularised, as the optimiser uses them);
  * 2 source, 3 target: the k-neighbour sample covariance BEFORE the eigen-regularisation.  cov: n*9 doubles. */
 int lsr_gicp_covariances(lsr_handle h, int which, double* cov);

@@ -287,6 +287,27 @@ class NormalDistributionsTransform : public Registration<PointSource, PointTarge
   void setNeighborhoodSearchMethod(NeighborSearchMethod m) { this->check(lsr_set_i32(this->h_, LSR_NEIGHBORHOOD, m), "setNeighborhoodSearchMethod"); }
   void setNumThreads(int n) { this->check(lsr_set_i32(this->h_, LSR_NUM_THREADS, n), "setNumThreads"); }  // accepted, ignored
   double getTransformationProbability() const { return this->last_.score; }
+  // ---- pose search: no guess inside NDT's basin of convergence (lidarslam_reg.h: NDT pose search) ----
+  // score[c] (and pairs[c], nullable) of the source at count poses (column-major 4x4 floats, 16 per pose), in one launch
+  bool scorePoses(const float* poses16, size_t count, double* score, double* pairs = nullptr) {
+    const int st = lsr_ndt_score_poses(this->h_, poses16, count, score, pairs);
+    this->check(st, "scorePoses");
+    return st == LSR_OK;
+  }
+  // the lattice around `center` scored, the distinct best refined as one candidate set, the winner adopted as after align().
+  // false: refused, or nothing kept (report->n_kept == 0); the previous pose stays in place.
+  bool searchPose(const Matrix4f& center, const lsr_pose_search_params& params, lsr_pose_search_report* report = nullptr) {
+    Matrix4f best = this->final_;
+    lsr_result res;
+    lsr_pose_search_report local;
+    lsr_pose_search_report* rep = report ? report : &local;
+    const int st = lsr_ndt_search_pose(this->h_, center.data(), &params, best.m, &res, rep);
+    this->check(st, "searchPose");
+    if (st != LSR_OK || rep->n_kept == 0) return false;
+    this->final_ = best;
+    this->last_ = res;
+    return true;
+  }
 };
 
 // pclomp::GeneralizedIterativeClosestPoint<PointSource,PointTarget>   scanmatcher_component.cpp:115-120

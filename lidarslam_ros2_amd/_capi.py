@@ -30,6 +30,8 @@ PCD_DEFLATE_MS = 15
 MAP_FILTER_KEY_BITS = 55
 MAP_WINDOW_MS = 22
 MAP_WINDOW_CELL_LIMIT = 1 << 24
+POSE_SEARCH_MS = 23
+POSE_SEARCH_MAX_POSES, POSE_SEARCH_MAX_KEPT = 1 << 20, 16
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2           # lsr_pcd_data
 PCD_DATA_KINDS = {"ascii": PCD_ASCII, "binary": PCD_BINARY, "binary_compressed": PCD_BINARY_COMPRESSED}
 PCD_LZF_CHUNK_BYTES = 4096
@@ -62,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "lsr_format_pcd", "lsr_save_pcd", "lsr_save_map_pcd", "lsr_lzf_deflate",
     "lsr_voxel_grid_filter_map", "lsr_assemble_map_filtered", "lsr_save_map_pcd_filtered",
     "lsr_map_window_around", "lsr_crop_map", "lsr_set_input_target_window",
+    "lsr_ndt_score_poses", "lsr_pose_lattice_poses", "lsr_select_poses", "lsr_ndt_search_pose",
 ]
 
 
@@ -116,6 +119,19 @@ class Pc2Layout(C.Structure):
 
 class MapWindow(C.Structure):
     _fields_ = [("leaf", C.c_float), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
+class PoseLattice(C.Structure):
+    _fields_ = [("n", C.c_int32 * 3), ("step", C.c_double * 3), ("n_yaw", C.c_int32), ("yaw_step", C.c_double)]
+
+
+class PoseSearchParams(C.Structure):
+    _fields_ = [("lattice", PoseLattice), ("top_k", C.c_int32), ("min_sep_m", C.c_double), ("min_sep_rad", C.c_double)]
+
+
+class PoseSearchReport(C.Structure):
+    _fields_ = [("n_candidates", C.c_int32), ("n_kept", C.c_int32), ("winner", C.c_int32), ("kept", C.c_int32 * 16),
+                ("coarse_score", C.c_double * 16), ("refined16", C.c_float * 256), ("refined", Result * 16)]
 
 
 class PcdInfo(C.Structure):
@@ -214,6 +230,10 @@ def load() -> C.CDLL:
     L.lsr_crop_map.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(MapWindow), vp, C.c_size_t, C.POINTER(Pc2Layout),
                                C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_set_input_target_window.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(MapWindow), C.POINTER(C.c_size_t)]
+    L.lsr_ndt_score_poses.argtypes = [vp, fp, C.c_size_t, dp, dp]
+    L.lsr_pose_lattice_poses.argtypes = [fp, C.POINTER(PoseLattice), fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lsr_select_poses.argtypes = [dp, fp, C.c_size_t, C.c_int, C.c_double, C.c_double, ip, C.POINTER(C.c_int)]
+    L.lsr_ndt_search_pose.argtypes = [vp, fp, C.POINTER(PoseSearchParams), fp, C.POINTER(Result), C.POINTER(PoseSearchReport)]
     L.lsr_parse_pcd_header.argtypes = [vp, C.c_size_t, C.POINTER(PcdInfo)]
     L.lsr_decode_pcd.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_load_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]

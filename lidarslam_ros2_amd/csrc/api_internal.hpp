@@ -41,6 +41,9 @@ int ensure_target_hash(lsr_handle h);
 int align_ndt_batch(lsr_handle_s** hs, int B, const float* guesses, float* finals, lsr_result* results, double* fitness_out = nullptr,
                     double max_range = 1.7976931348623157e308);
 
+// the problem record and table mode (lsr::NdtTableMode; tab_bytes: the LDS image's size in that mode, else 0) of a pose-scoring launch
+int ndt_score_problem(lsr_handle_s* h, int other_lds, NdtProblem* P, int* tab, int* tab_bytes);
+
 // ---- inputs.hip
 int assemble_frames(lsr_handle h, int n_frames, const void* const* frames, const size_t* counts, size_t stride_bytes, const float* poses16,
                     bool on_device, DeviceCloud& out);

@@ -171,6 +171,7 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_MAP_FILTER_CENTROID_MS: case LSR_MAP_FILTER_WRITE_MS:
       *v = h->map_filter.ms[key - LSR_MAP_FILTER_BBOX_MS]; return LSR_OK;
     case LSR_MAP_WINDOW_MS: *v = h->map_window.ms; return LSR_OK;
+    case LSR_POSE_SEARCH_MS: *v = h->pose_search.ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "grid_device.hpp"
+#include "ndt_canon.hpp"
 #include "ndt_point.hpp"
 #include "sort.hpp"
 #include "voxel_device.hpp"   // wave_sum
@@ -393,13 +394,7 @@ __device__ __forceinline__ void build_request(NdtState* S, double* f /*8*/, floa
   barrier_lds_only();
 }
 
-// Ordering of LDS traffic inside ONE wave: its lanes run in lockstep and the LDS unit executes a wave's operations in
-// order, so "lane 0 wrote, every lane reads" needs no workgroup barrier — only that the compiler keeps the order and the
-// writes have been issued.
-__device__ __forceinline__ void wave_lds_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
+// (wave_lds_fence(), the ordering of LDS traffic inside ONE wave: ndt_canon.hpp)
 
 // build_request() for a caller that runs the whole controller step on wave 0 (quad kernel): same work, the 64 lanes of
 // one wave, no workgroup barrier.  ent_a = k_angle_entries[lane], ent_b = k_angle_entries[64 + lane] (lane < 8).
@@ -748,37 +743,7 @@ __device__ __forceinline__ double uniform_d(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// sum partner inside a quad of lanes via DPP quad_perm (no LDS traffic): CTRL 0xB1 = [1,0,3,2], 0x4E = [2,3,0,1]
-template <int CTRL>
-__device__ __forceinline__ double dpp_quad_xor(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-template <int NOFF>
-struct Offsets;
-template <>
-struct Offsets<1> {
-  static __device__ __forceinline__ void get(int o, int& dx, int& dy, int& dz) { dx = dy = dz = 0; }
-};
-template <>
-struct Offsets<7> {
-  static __device__ __forceinline__ void get(int o, int& dx, int& dy, int& dz) {
-    dx = (o == 1) - (o == 2);
-    dy = (o == 3) - (o == 4);
-    dz = (o == 5) - (o == 6);
-  }
-};
-template <>
-struct Offsets<27> {
-  static __device__ __forceinline__ void get(int o, int& dx, int& dy, int& dz) {
-    dx = o / 9 - 1;
-    dy = (o / 3) % 3 - 1;
-    dz = o % 3 - 1;
-  }
-};
+// (dpp_quad_xor and the neighbourhood offsets Offsets<NOFF>: ndt_canon.hpp, shared with the pose-scoring kernel)
 
 // ===========================================================================================
 // The canonical sum of a pass: one input, one answer
@@ -798,58 +763,8 @@ struct Offsets<27> {
 //    chunks arrive nor the workgroup that owns a chunk can change a bit.
 // What this buys: lsr_align of one registration (quad kernel) and the same registration inside lsr_align_batch (lane kernel)
 // walk the same Newton / More-Thuente trajectory to the same final_T; tests assert array_equal, not a tolerance.
-namespace canon {
-constexpr int TILE_PITCH = 68;    // floats per row of a staging tile: rows 16-byte aligned, consecutive rows four banks apart
-constexpr int TILE_ROWS = 16;     // values staged at a time (a Hessian pass goes through the tile twice)
-constexpr int TILE_FLOATS = TILE_ROWS * TILE_PITCH;
-
-__device__ __forceinline__ double quantum(const int k) { return __hiloint2double((1023 + 62 - 31 * (k + 1)) << 20, 0); }
-__device__ __forceinline__ double iquantum(const int k) { return __hiloint2double((1023 - 62 + 31 * (k + 1)) << 20, 0); }
-
-// piece k of the exact split of t: the pieces of one value can be formed independently of each other (five lanes, one piece
-// each) because t minus its multiple-of-q_(k-1) part is exact in fp64.  |t| >= 2^62 or NaN: no piece, *poison raised.
-__device__ __forceinline__ int piece(const double t, const int k, bool* poison) {
-  *poison = !(fabs(t) < 4611686018427387904.0);
-  if (*poison) return 0;
-  double r = t;
-  if (k > 0) r = t - trunc(t * iquantum(k - 1)) * quantum(k - 1);   // |r| < q_(k-1) = 2^31 q_k, exact
-  return (int)(r * iquantum(k));                                     // truncation toward zero
-}
-
-// 8 consecutive fp32 terms at p (16-byte aligned, LDS), lanes l & 7 = run: the chunk total of a gradient-only pass, in every lane
-__device__ __forceinline__ double reduce_grad(const float* p) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 a = *reinterpret_cast<const f4*>(p), b = *reinterpret_cast<const f4*>(p + 4);
-  double t = (double)a.x;
-  t += (double)a.y; t += (double)a.z; t += (double)a.w;
-  t += (double)b.x; t += (double)b.y; t += (double)b.z; t += (double)b.w;
-  t += dpp_quad_xor<0xB1>(t);    // runs {0<->1, 2<->3, ...}
-  t += dpp_quad_xor<0x4E>(t);    // pairs of runs
-  t += dpp_quad_xor<0x141>(t);   // row_half_mirror: lane 7 - l of the 8-lane group = the other quad (whose lanes all hold its sum)
-  return t;
-}
-// 16 consecutive fp32 terms at p, lanes l & 3 = run: the chunk total of a pass with Hessian, in every lane of the quad
-__device__ __forceinline__ double reduce_hess(const float* p) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 a = *reinterpret_cast<const f4*>(p), b = *reinterpret_cast<const f4*>(p + 4), c = *reinterpret_cast<const f4*>(p + 8),
-           d = *reinterpret_cast<const f4*>(p + 12);
-  double t = (double)a.x;
-  t += (double)a.y; t += (double)a.z; t += (double)a.w;
-  t += (double)b.x; t += (double)b.y; t += (double)b.z; t += (double)b.w;
-  t += (double)c.x; t += (double)c.y; t += (double)c.z; t += (double)c.w;
-  t += (double)d.x; t += (double)d.y; t += (double)d.z; t += (double)d.w;
-  t += dpp_quad_xor<0xB1>(t);
-  t += dpp_quad_xor<0x4E>(t);
-  return t;
-}
-// piece k of chunk total t of value v -> a workgroup's LDS bins [NDT_NBINS][32] (poison: slot 31 of bin 0, raised by the k = 0 caller)
-__device__ __forceinline__ void add_piece_lds(unsigned long long* ibin, const int v, const int k, const double t) {
-  bool poison;
-  const int m = piece(t, k, &poison);
-  if (m != 0) atomicAdd(&ibin[k * 32 + v], (unsigned long long)(long long)m);
-  if (poison && k == 0) atomicAdd(&ibin[31], 1ull);
-}
-}  // namespace canon
+// The functions — the trees, the split, the fold — are namespace canon of ndt_canon.hpp: the pose-scoring kernel (pose_search.hip)
+// forms the score and the pair count of a pose with them and returns the bits a derivative pass at that pose returns.
 
 // The derivative pass (K3) is preceded, in the same launch, by the controller step (K4) that consumes the PREVIOUS pass.
 //
@@ -939,9 +854,7 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
     }
     if (tid < NDT_NBINS * 32) {
       const int k = tid >> 5;
-      // quantum of bin k: 2^(62 - 31 (k + 1)); an int64 below 2^53 converts exactly
-      const double q = __hiloint2double((1023 + 62 - 31 * (k + 1)) << 20, 0);
-      s_bin[k][tid & 31] = (double)msum * q;
+      s_bin[k][tid & 31] = canon::bin_value(msum, k);   // quantum of bin k: 2^(62 - 31 (k + 1)); an int64 below 2^53 converts exactly
       s_ibin[tid] = 0ull;
     }
     if (tid < STATE_Q) s_state_q[tid] = stq;
@@ -984,8 +897,9 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
     if (seq > 0) {
       if (tid < NDT_NRED) {
         // fold the bins smallest quantum first (fixed order); a raised poison slot (overflow / NaN partial) poisons all sums
-        double t = (((s_bin[4][tid] + s_bin[3][tid]) + s_bin[2][tid]) + s_bin[1][tid]) + s_bin[0][tid];
-        if (s_bin[0][31] != 0.0 || s_bin[1][31] != 0.0) t = __longlong_as_double(0x7FF8000000000000ll);
+        const double b4 = s_bin[4][tid], b3 = s_bin[3][tid], b2 = s_bin[2][tid], b1 = s_bin[1][tid], b0 = s_bin[0][tid];
+        double t = canon::fold(b0, b1, b2, b3, b4);
+        if (s_bin[0][31] != 0.0 || s_bin[1][31] != 0.0) t = canon::poisoned();
         s_sum[tid] = t;
       }
       wave_lds_fence();
@@ -1276,11 +1190,7 @@ __global__ __launch_bounds__(4 * PTS) void ndt_eval_quad_kernel(const NdtProblem
 //      launch to launch as the registrations of a set finish (run_ndt_feeder).
 //  tab_bytes: size of the table region at the start of the dynamic LDS (largest image of the set, multiple of 1 KiB); the
 //      staging tiles follow it.
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const v4f LdsV4;
-typedef __attribute__((address_space(1))) const v4f GlbV4;
-typedef __attribute__((address_space(1))) const float GlbFloat;
-typedef __attribute__((address_space(1))) const int GlbInt;
+// (v4f, LdsV4, GlbV4, GlbFloat, GlbInt: ndt_canon.hpp)
 
 //  SPLIT (round 6; single scans that do not fill the chip with one lane per point: cfg 5's 120k points are 1.8 waves per SIMD, 73 % of
 //      their cycles waiting on the dependent gather -> exp -> weight chain of seven neighbours one after the other): TWO WAVES per
@@ -1334,7 +1244,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
       msum = ((m[0] + m[1]) + (m[2] + m[3])) + ((m[4] + m[5]) + (m[6] + m[7]));
     }
     if (tid < NDT_NBINS * 32) {
-      s_bin[tid >> 5][tid & 31] = (double)msum * canon::quantum(tid >> 5);
+      s_bin[tid >> 5][tid & 31] = canon::bin_value(msum, tid >> 5);
       s_ibin[tid] = 0ull;
     }
     if (tid < STATE_Q) s_state_q[tid] = stq;
@@ -1366,8 +1276,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
   if (tid < 64) {
     if (seq > 0) {
       if (tid < NDT_NRED) {
-        double t = (((s_bin[4][tid] + s_bin[3][tid]) + s_bin[2][tid]) + s_bin[1][tid]) + s_bin[0][tid];
-        if (s_bin[0][31] != 0.0 || s_bin[1][31] != 0.0) t = __longlong_as_double(0x7FF8000000000000ll);
+        const double b4 = s_bin[4][tid], b3 = s_bin[3][tid], b2 = s_bin[2][tid], b1 = s_bin[1][tid], b0 = s_bin[0][tid];
+        double t = canon::fold(b0, b1, b2, b3, b4);
+        if (s_bin[0][31] != 0.0 || s_bin[1][31] != 0.0) t = canon::poisoned();
         s_sum[tid] = t;
       }
       wave_lds_fence();

@@ -599,6 +599,21 @@ int lsr::align_ndt_batch(lsr_handle* hs, int B, const float* guesses, float* fin
   return LSR_OK;
 }
 
+// The problem record and the table mode of a pose-scoring launch (pose_search.hip) on h's target and source: what choose_table_mode
+// gives the object (LSR_NDT_TABLE_MODE included), with the LDS table only where it fits next to `other_lds` bytes of the kernel's own.
+int lsr::ndt_score_problem(lsr_handle h, int other_lds, NdtProblem* P, int* tab, int* tab_bytes) {
+  NdtLaunchCfg cfg;
+  cfg.neighborhood = h->ndt.neighborhood;
+  lsr_handle one[1] = {h};
+  choose_table_mode(h, one, 1, cfg);
+  const VoxelGridDev& g = h->target->grid;
+  if (cfg.tab == NDT_TAB_LDS && cfg.lds_bytes + other_lds > device_lds_bytes(h->device)) cfg.tab = g.dense ? NDT_TAB_DENSE : NDT_TAB_COMPACT;
+  fill_problem(*P, h, nullptr, nullptr, cfg);
+  *tab = cfg.tab;
+  *tab_bytes = (cfg.tab == NDT_TAB_LDS) ? g.lds_bytes : 0;
+  return LSR_OK;
+}
+
 // ---- NDT inspection entries: the grid as built, one derivative pass at a given pose ---------------------------------------
 extern "C" {
 

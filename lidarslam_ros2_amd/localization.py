@@ -19,6 +19,7 @@ object.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -62,6 +63,7 @@ class Localizer:
         self.n_recuts = 0                  # cuts after the first
         self.n_target = 0
         self._whole_map_set = False
+        self.last_search = None            # report of the last relocalize (Registration.searchPose)
 
     # -- the map -------------------------------------------------------------------------------------------------------------------
     def set_map(self, records):
@@ -121,6 +123,49 @@ class Localizer:
             if outside:
                 self.lost = True
             if outside or needs_recut(t, self.center, p.slack):
+                self._cut(t)
+                self.n_recuts += 1
+        return self.pose
+
+    # -- without a guess -----------------------------------------------------------------------------------------------------------
+    def relocalize(self, payload, n_points: int, center=None, half_extent=(10.0, 10.0, 0.0), step=(1.0, 1.0, 1.0),
+                   yaw_half_range: float = math.pi, yaw_step: float = math.radians(5.0), top_k: int = 16,
+                   min_sep=(0.9, math.radians(7.5))) -> np.ndarray:
+        """Find the pose of one scan with no guess inside NDT's basin of convergence (Registration.searchPose): the scan's NDT score
+        over the lattice center +- half_extent (metres per axis, `step` apart) x yaw +- yaw_half_range (yaw_step apart), the distinct
+        best top_k refined, the winner adopted.  `center` (4x4): defaults to the current pose.  The window is cut around the centre with
+        reach + slack + half_extent, so every candidate finds its target.  Clears `lost`, applies the re-cut rule, keeps the report in
+        `last_search`.  Nothing kept (no candidate puts a point into a voxel): raises, and pose, window and `lost` stay as they were."""
+        if self.map is None:
+            raise RuntimeError("set_map or load_map first")
+        if self.p.registration_method != "NDT":
+            raise RuntimeError("relocalize needs an NDT registration object")
+        p = self.p
+        C0 = np.asarray(self.pose if center is None else center, np.float32).reshape(4, 4)
+        half_extent = np.asarray(half_extent, np.float64)
+        n = [2 * int(round(half_extent[k] / step[k])) + 1 if step[k] > 0 else 1 for k in range(3)]
+        n_yaw = max(1, 2 * int(round(yaw_half_range / yaw_step)) + (0 if yaw_half_range >= math.pi else 1)) if yaw_step > 0 else 1
+        if self.use_window:
+            half = np.asarray(p.reach, np.float64) + np.asarray(p.slack, np.float64) + half_extent
+            window = mapWindowAround(C0[:3, 3], half, self._leaf())
+            n_target = self.reg.setInputTargetWindow(self.map, window, PC2_XYZI)   # keeps nothing: raises, the previous target stays
+        elif not self._whole_map_set:
+            records = _as_float_records(self.map, PC2_XYZI[0])
+            self.reg.setInputTarget(records)
+            self.n_target, self._whole_map_set = int(records.shape[0]), True
+        self.reg.setInputSourcePointCloud2(payload, n_points, PC2_XYZI[0], PC2_XYZI[1], p.scan_min_range, p.scan_max_range, p.vg_size_for_input)
+        pose, _, report = self.reg.searchPose(C0, n, step, n_yaw, yaw_step, top_k, min_sep[0], min_sep[1])
+        if pose is None:
+            if self.use_window and self.window is not None:   # the target the tracker had: the next receive_cloud finds it again
+                self.reg.setInputTargetWindow(self.map, self.window, PC2_XYZI)
+            raise RuntimeError("relocalize: no candidate pose puts a scan point into a map voxel")
+        self.last_search = report
+        self.pose = pose
+        self.lost = False
+        if self.use_window:
+            self.window, self.center, self.n_target = window, np.asarray(C0[:3, 3], np.float64).copy(), n_target
+            t = self.pose[:3, 3]
+            if not self.window.contains(t) or needs_recut(t, self.center, p.slack):
                 self._cut(t)
                 self.n_recuts += 1
         return self.pose

@@ -46,6 +46,44 @@ def mapWindowAround(center, half_extent, leaf: float) -> MapWindow:
     return MapWindow(float(w.leaf), tuple(int(v) for v in w.lo), tuple(int(v) for v in w.hi))
 
 
+def _poses_to_col16(poses) -> np.ndarray:
+    """(count, 4, 4) row/col indexed -> (count, 16) in Eigen's column-major order."""
+    P = np.asarray(poses, np.float32)
+    if P.ndim == 2:
+        P = P[None]
+    if P.ndim != 3 or P.shape[1:] != (4, 4):
+        raise ValueError("poses must be (count, 4, 4)")
+    return np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1, 16)
+
+
+def poseLattice(center, n=(1, 1, 1), step=(1.0, 1.0, 1.0), n_yaw: int = 1, yaw_step: float = 0.0) -> np.ndarray:
+    """The pose lattice of lsr_pose_lattice_poses around `center` (4x4): n[0] x n[1] x n[2] translations `step` apart times n_yaw
+    headings yaw_step apart, all centred -> (count, 4, 4) fp32, candidate ((m n[2] + k) n[1] + j) n[0] + i.  Needs no device."""
+    c = _mat_to_col16(center)
+    L = capi.PoseLattice((C.c_int32 * 3)(*[int(v) for v in n]), (C.c_double * 3)(*[float(v) for v in step]), int(n_yaw), float(yaw_step))
+    lib = capi.load()
+    count = C.c_size_t(0)
+    cp = c.ctypes.data_as(C.POINTER(C.c_float))
+    capi.check(lib.lsr_pose_lattice_poses(cp, C.byref(L), None, 0, C.byref(count)), "poseLattice")
+    out = np.zeros((count.value, 16), np.float32)
+    capi.check(lib.lsr_pose_lattice_poses(cp, C.byref(L), out.ctypes.data_as(C.POINTER(C.c_float)), count.value, C.byref(count)), "poseLattice")
+    return np.ascontiguousarray(out.reshape(-1, 4, 4).transpose(0, 2, 1))
+
+
+def selectPoses(score, poses, top_k: int = 16, min_sep_m: float = 0.9, min_sep_rad: float = 0.1308996938995747) -> np.ndarray:
+    """The distinct best of a scored pose list (lsr_select_poses): indices, best first.  Needs no device."""
+    s = np.ascontiguousarray(score, np.float64).reshape(-1)
+    p = _poses_to_col16(poses)
+    if p.shape[0] != s.shape[0]:
+        raise ValueError("one score per pose")
+    kept = np.zeros(capi.POSE_SEARCH_MAX_KEPT, np.int32)
+    n = C.c_int(0)
+    capi.check(capi.load().lsr_select_poses(s.ctypes.data_as(C.POINTER(C.c_double)), p.ctypes.data_as(C.POINTER(C.c_float)), s.shape[0],
+                                            int(top_k), float(min_sep_m), float(min_sep_rad), kept.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            C.byref(n)), "selectPoses")
+    return kept[:n.value].copy()
+
+
 def _window_struct(window) -> capi.MapWindow:
     leaf, lo, hi = window
     return capi.MapWindow(float(leaf), (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]))
@@ -1064,6 +1102,48 @@ class NormalDistributionsTransform(Registration):
         if with_pairs:
             return score.value, g, H, pairs.value
         return score.value, g, H
+
+    # pose search ---------------------------------------------------------------------------
+    poseLattice = staticmethod(poseLattice)
+    selectPoses = staticmethod(selectPoses)
+
+    def scorePoses(self, poses):
+        """The NDT score and pair count of the source at every pose of `poses` ((count, 4, 4)) in one launch (lsr_ndt_score_poses):
+        the bits derivatives(p, T=pose, compute_hessian=False, with_pairs=True) returns per pose.  -> (score, pairs), fp64."""
+        p = _poses_to_col16(poses)
+        score, pairs = np.zeros(p.shape[0]), np.zeros(p.shape[0])
+        capi.check(self._lib.lsr_ndt_score_poses(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0],
+                                                 score.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 pairs.ctypes.data_as(C.POINTER(C.c_double))), "scorePoses")
+        return score, pairs
+
+    def poseSearchMs(self) -> float:
+        """hipEvent time [ms] of the last scorePoses / searchPose's scoring launch on this object (setProfiling(True)), else 0."""
+        return self._getf(capi.POSE_SEARCH_MS)
+
+    def searchPose(self, center, n=(1, 1, 1), step=(1.0, 1.0, 1.0), n_yaw: int = 1, yaw_step: float = 0.0, top_k: int = 16,
+                   min_sep_m: float = 0.9, min_sep_rad: float = 0.1308996938995747):
+        """lsr_ndt_search_pose: the lattice around `center` scored, the distinct best top_k refined as one candidate set, the winner
+        by trans_probability.  -> (pose, result, report): pose (4, 4) fp32 or None when nothing was kept; result as last_result;
+        report: n_candidates, kept, coarse_score, refined (n_kept, 4, 4), results (one dict per kept candidate), winner."""
+        c = _mat_to_col16(center)
+        prm = capi.PoseSearchParams(capi.PoseLattice((C.c_int32 * 3)(*[int(v) for v in n]), (C.c_double * 3)(*[float(v) for v in step]),
+                                                     int(n_yaw), float(yaw_step)), int(top_k), float(min_sep_m), float(min_sep_rad))
+        best = np.zeros(16, np.float32)
+        rep = capi.PoseSearchReport()
+        capi.check(self._lib.lsr_ndt_search_pose(self._h, c.ctypes.data_as(C.POINTER(C.c_float)), C.byref(prm),
+                                                 best.ctypes.data_as(C.POINTER(C.c_float)), C.byref(self._last), C.byref(rep)), "searchPose")
+        k = int(rep.n_kept)
+
+        def as_dict(r):
+            return dict(converged=bool(r.converged), iterations=int(r.iterations), score=float(r.score),
+                        n_evaluations=int(r.n_evaluations), n_correspondences=int(r.n_correspondences), gpu_ms=float(r.gpu_ms))
+
+        refined = np.ctypeslib.as_array(rep.refined16).reshape(16, 4, 4)[:k].transpose(0, 2, 1).copy()
+        report = dict(n_candidates=int(rep.n_candidates), n_kept=k, winner=int(rep.winner),
+                      kept=np.array(rep.kept[:k], np.int32), coarse_score=np.array(rep.coarse_score[:k], np.float64),
+                      refined=refined, results=[as_dict(rep.refined[e]) for e in range(k)])
+        return (_col16_to_mat(best) if k > 0 else None), self.last_result, report
 
 
 class GeneralizedIterativeClosestPoint(Registration):
