@@ -993,6 +993,29 @@ int lsr_debug_angle_tables(const double* p6, int d1_sign, float* jang_ref, float
  * lsr_align starts from guess16 (column-major 4x4, nullable = identity) — the fp32 Euler angles of Eigen's eulerAngles(0,1,2),
  * alias branch included (a rotation whose roll comes out positive is returned as (roll - pi, pi - pitch, yaw -+ pi), negated). */
 int lsr_debug_guess_pose(const float* guess16, double* p6);
+/* The three entries below inspect the on-device NDT controller (Newton step, More-Thuente line search, 6x6 solve) apart from the
+ * derivative pass: each launches one workgroup of one wave that calls the device functions of the derivative kernels as they are.
+ * Any registration object serves as h (its device and stream are used; no target or source is needed).  A null pointer or a count
+ * outside its range is LSR_ERR_INVALID_ARGUMENT before any device is touched.
+ *
+ * The controller on prepared sums.  The state starts as lsr_align leaves it before its first launch, with the pose p6 given
+ * directly.  rows: n_rows x 29 doubles, each the reduced sums of one derivative pass as the kernels lay them out (score, gradient[6],
+ * pair count, the upper triangle of the Hessian row by row [21]).  Row after row, until the controller has finished, the sums are
+ * handed to the controller step and one trace row of LSR_NDT_REPLAY_TRACE doubles is written: phase, want_hessian, the request
+ * flags, done, converged, nr_iterations, n_evals, n_passes, step_iterations, open_interval, interval_converged, a_t, a_l, f_l, g_l,
+ * a_u, f_u, g_u, phi_0, d_phi_0, p[6], x_t[6], dir[6], score, g[6], trans_probability, last_pairs.  *n_used = rows consumed;
+ * trace rows beyond it are zero.  1 <= n_rows <= LSR_NDT_REPLAY_MAX_ROWS, n_points >= 1. */
+#define LSR_NDT_REPLAY_MAX_ROWS 512
+#define LSR_NDT_REPLAY_TRACE 47
+#define LSR_DEBUG_MAX_COUNT (1 << 20)
+int lsr_debug_ndt_controller_replay(lsr_handle h, const double* p6, double step_size, double trans_eps, int max_iterations,
+                                    int n_points, const double* rows, int n_rows, double* trace, int* n_used);
+/* delta6[6 i ..] = the Newton step -H^-1 g of system i (Hu21[21 i ..] the upper triangle row by row, g6[6 i ..]) by the controller's
+ * one-wave elimination, the systems one after another.  1 <= count <= LSR_DEBUG_MAX_COUNT. */
+int lsr_debug_ndt_solve6(lsr_handle h, const double* Hu21, const double* g6, int count, double* delta6);
+/* quot[i] = a[i] / b[i] and root[i] = sqrt(a[i]) by the line search's fast fp64 division and square root.
+ * 1 <= count <= LSR_DEBUG_MAX_COUNT. */
+int lsr_debug_mt_math(lsr_handle h, const double* a, const double* b, int count, double* quot, double* root);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ PCD_READ_MAX_LINE_BYTES = 1024
 ERR_NOT_IMPLEMENTED, ERR_INDEX_OVERFLOW = -6, -7
 ERR_IO = -9
 PCD_ASCII_MAX_LINE_BYTES, PCD_ASCII_MAX_HEADER_BYTES = 60, 256
+NDT_REPLAY_MAX_ROWS, NDT_REPLAY_TRACE, DEBUG_MAX_COUNT = 512, 47, 1 << 20
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
  HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED,
  MAP_ASSEMBLY_FORM) = range(32, 50)
@@ -52,7 +53,7 @@ EXPORTED_SYMBOLS = [
     "lsr_share_target", "lsr_wait_stream", "lsr_align", "lsr_align_batch",
     "lsr_get_final_transformation", "lsr_has_converged", "lsr_get_fitness_score", "lsr_search_loop", "lsr_ndt_grid_info",
     "lsr_ndt_grid_dump", "lsr_ndt_grid_centroids", "lsr_ndt_derivatives", "lsr_ndt_derivatives_pairs", "lsr_gicp_covariances", "lsr_nearest_neighbors", "lsr_get_profile",
-    "lsr_debug_angle_tables", "lsr_debug_guess_pose", "lsr_set_input_source_pc2", "lsr_get_source_pc2", "lsr_voxel_grid_filter_pc2", "lsr_shard_range", "lsr_comm_unique_id", "lsr_comm_create", "lsr_comm_destroy", "lsr_align_batch_sharded",
+    "lsr_debug_angle_tables", "lsr_debug_guess_pose", "lsr_debug_ndt_controller_replay", "lsr_debug_ndt_solve6", "lsr_debug_mt_math", "lsr_set_input_source_pc2", "lsr_get_source_pc2", "lsr_voxel_grid_filter_pc2", "lsr_shard_range", "lsr_comm_unique_id", "lsr_comm_create", "lsr_comm_destroy", "lsr_align_batch_sharded",
     "lsr_shard_plan", "lsr_align_batch_planned", "lsr_align_fitness_batch",
     "lsr_set_input_target_batch", "lsr_set_input_source_batch", "lsr_get_fitness_score_batch", "lsr_set_input_target_bcast", "lsr_get_source_pc2_device",
     "lsr_comm_all_gather_records", "lsr_set_input_target_frames_filtered", "lsr_prepare_target", "lsr_gicp_linearize",
@@ -254,6 +255,9 @@ def load() -> C.CDLL:
     L.lsr_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
     L.lsr_debug_angle_tables.argtypes = [dp, C.c_int, fp, fp, fp, fp]
     L.lsr_debug_guess_pose.argtypes = [fp, dp]
+    L.lsr_debug_ndt_controller_replay.argtypes = [vp, dp, C.c_double, C.c_double, C.c_int, C.c_int, dp, C.c_int, dp, C.POINTER(C.c_int)]
+    L.lsr_debug_ndt_solve6.argtypes = [vp, dp, dp, C.c_int, dp]
+    L.lsr_debug_mt_math.argtypes = [vp, dp, dp, C.c_int, dp, dp]
     L.lsr_set_input_source_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_double, C.c_float, C.c_int,
                                            C.POINTER(C.c_size_t)]
     L.lsr_get_source_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.POINTER(C.c_size_t)]

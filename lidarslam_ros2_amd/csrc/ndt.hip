@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "api_internal.hpp"   // the handle check of the inspection entries at the bottom
 #include "grid_device.hpp"
 #include "ndt_canon.hpp"
 #include "ndt_point.hpp"
@@ -157,9 +158,11 @@ typedef __attribute__((address_space(3))) double LdsDouble;
 // fp64 division / square root for the More-Thuente interpolation formulas, on ONE lane with the rest of the chip
 // waiting: hardware seed (v_rcp_f64 / v_rsq_f64) + two Newton steps + one residual correction = ~10 dependent
 // instructions instead of the ~35 of the IEEE sequences (div_scale / div_fmas / div_fixup).  Results are within 1 ulp
-// of the correctly rounded ones; badly scaled operands take the IEEE path.
+// of the correctly rounded ones; badly scaled operands take the IEEE path (test_ndt_controller_gpu.py holds both to it).
 __device__ __forceinline__ double mt_div(double a, double b) {
-  if (!(fabs(b) > 1e-290 && fabs(b) < 1e290)) return a / b;  // zero / denormal / huge / NaN divisor: the IEEE sequence
+  // zero / denormal / huge / NaN divisor, or a dividend so large that a * (1 / b) could overflow (the residual step would make
+  // inf - inf = NaN of it) or not finite: the IEEE sequence
+  if (!(fabs(b) > 1e-290 && fabs(b) < 1e290 && fabs(a) < 1e18)) return a / b;
   double r = __builtin_amdgcn_rcp(b);
   r = fma(fma(-b, r, 1.0), r, r);
   r = fma(fma(-b, r, 1.0), r, r);
@@ -176,6 +179,12 @@ __device__ __forceinline__ double mt_sqrt(double x) {
 }
 
 // ---- More-Thuente helpers ----
+// std::max(std::min(a, hi), lo) as the reference writes it: a NaN step stays NaN (fmin / fmax would return the bound, and the search
+// would go on from step_max where the reference's pose is NaN); any other a gives the bits of fmax(fmin(a, hi), lo).
+__device__ __forceinline__ double mt_clamp(double a, double lo, double hi) {
+  a = (hi < a) ? hi : a;
+  return (a < lo) ? lo : a;
+}
 __device__ __forceinline__ double mt_trial_value(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u, double a_t,
                                  double f_t, double g_t) {
   if (f_t > f_l) {
@@ -225,8 +234,9 @@ __device__ __forceinline__ bool mt_update_interval(MtInterval& I, double a_t, do
 
 // delta = H^{-1} (-g) by Gauss-Jordan elimination with partial pivoting on ONE WAVE: lane 8 r + c holds element (r, c) of the
 // augmented 6 x 7 matrix [H | -g] in a register, every step is a handful of cross-lane reads.  The reference calls
-// JacobiSVD::solve; for a non-singular 6x6 both give H^{-1} b.  A column whose pivot vanishes is dropped = its unknown set to
-// 0, which is the SVD's minimum-norm answer for the degenerate all-zero Hessian of a scan that overlaps no voxel.
+// JacobiSVD::solve; for a non-singular 6x6 both give H^{-1} b.  A column whose pivot vanishes (at most 6 eps of the largest |H_ij|,
+// the SVD's own rank threshold) is dropped = its unknown set to 0, which is the SVD's minimum-norm answer wherever the vanishing
+// direction is decoupled from the rest: the all-zero Hessian of a scan that overlaps no voxel, a zero row and column.
 // Hu: the 21 values of the upper triangle, row-major (0,0..5) (1,1..5) ... (5,5), g: the gradient, out[0..5] receives delta
 // (all three in LDS; the caller fences the wave's LDS traffic around the call).
 // Why a wave and not one lane with the matrix in registers (rounds 1-2: ~166 VGPRs, fully unrolled): the register count of a
@@ -257,7 +267,9 @@ __device__ __forceinline__ void solve6_wave(const LdsDouble* Hu, const LdsDouble
       const double t = fabs(__shfl(v, i * 8 + k, 64));
       if (t > best) { best = t; piv = i; }
     }
-    if (!(best > scale * 1e-300) || !(best > 0)) { dropped |= (1u << k); continue; }
+    // JacobiSVD::solve treats singular values <= 6 eps s_max as zero; a pivot that small against the largest |H_ij| is a direction the
+    // data does not observe.  A NaN pivot is not dropped: it spreads, the step comes out NaN and the align ends unconverged.
+    if (best <= 6.0 * 2.220446049250313e-16 * scale) { dropped |= (1u << k); continue; }
     // bring the pivot row to position k
     const double from_piv = __shfl(v, piv * 8 + c, 64), from_k = __shfl(v, k * 8 + c, 64);
     v = (r == k) ? from_piv : ((r == piv) ? from_k : v);
@@ -531,7 +543,7 @@ __device__ __forceinline__ int ndt_controller_mt(LdsState* S, const LdsDouble* s
       a_t = mt_trial_value(I.a_l, I.f_l, I.g_l, I.a_u, I.f_u, I.g_u, a_t, psi_t, d_psi_t);
     else
       a_t = mt_trial_value(I.a_l, I.f_l, I.g_l, I.a_u, I.f_u, I.g_u, a_t, phi_t, d_phi_t);
-    a_t = fmax(fmin(a_t, step_max), step_min);
+    a_t = mt_clamp(a_t, step_min, step_max);
 #pragma unroll
     for (int i = 0; i < 6; i++) S->x_t[i] = p[i] + dir[i] * a_t;
     S->a_t = a_t;
@@ -629,7 +641,7 @@ __device__ __forceinline__ int ndt_newton_begin(LdsState* S, const LdsDouble* de
 #pragma unroll
     for (int i = 0; i < 6; i++) dir[i] = -dir[i];
   }
-  const double a_t = fmax(fmin(nrm, step_max), step_min);
+  const double a_t = fmax(fmin(nrm, step_max), step_min);  // nrm is not NaN here (tested above): the bits of mt_clamp, two instructions
   S->d_phi_0 = d_phi_0;
   S->a_l = 0; S->a_u = 0;
   S->f_l = 0; S->f_u = 0;  // psi(0) = phi_0 - phi_0 - mu*d_phi_0*0
@@ -1551,6 +1563,75 @@ extern "C" int lsr_debug_timing_buffer(long long** out) {
 namespace {
 #endif
 
+// ===========================================================================================
+// Inspection kernels of the controller (lsr_debug_ndt_controller_replay, lsr_debug_ndt_solve6, lsr_debug_mt_math): one workgroup of
+// one wave each, around the device functions above as the derivative kernels call them.
+// ===========================================================================================
+constexpr int NDT_REPLAY_MAX_ROWS = LSR_NDT_REPLAY_MAX_ROWS;
+constexpr int NDT_REPLAY_ROW = 29;         // the sums of a pass: score, g[6], pairs, upper-triangle H[21]
+constexpr int NDT_REPLAY_TRACE = LSR_NDT_REPLAY_TRACE;   // doubles per consumed row (lidarslam_reg.h lists them)
+
+// The controller fed with prepared sums instead of a derivative pass: per row, what wave 0 of a launch does between folding the
+// accumulator bank and building the next request.  The request flags (pad1) are cleared after they are traced, as build_request does.
+__global__ __launch_bounds__(64) void ndt_controller_replay_kernel(const NdtState st, const double* __restrict__ rows, int n_rows,
+                                                                   double* __restrict__ trace, int* __restrict__ n_used) {
+  constexpr int STATE_Q = (int)(sizeof(NdtState) / 16);
+  __shared__ uint4 s_state_q[STATE_Q];
+  __shared__ double s_sum[NDT_NRED];
+  const int lane = threadIdx.x;
+  const uint4* src = reinterpret_cast<const uint4*>(&st);
+  for (int k = lane; k < STATE_Q; k += 64) s_state_q[k] = src[k];
+  wave_lds_fence();
+  LdsState* L = (LdsState*)reinterpret_cast<unsigned int*>(s_state_q);
+  int used = 0;
+  for (int r = 0; r < n_rows; r++) {
+    if (uniform_i(L->done)) break;
+    if (lane < NDT_NRED) s_sum[lane] = (lane < NDT_REPLAY_ROW) ? rows[(size_t)r * NDT_REPLAY_ROW + lane] : 0.0;
+    wave_lds_fence();
+    ndt_controller_wave0(L, (const LdsDouble*)s_sum);
+    wave_lds_fence();
+    if (lane == 0) {
+      double* t = trace + (size_t)r * NDT_REPLAY_TRACE;
+      t[0] = (double)L->phase; t[1] = (double)L->want_hessian; t[2] = (double)L->pad1; t[3] = (double)L->done;
+      t[4] = (double)L->converged; t[5] = (double)L->nr_iterations; t[6] = (double)L->n_evals; t[7] = (double)L->n_passes;
+      t[8] = (double)L->step_iterations; t[9] = (double)L->open_interval; t[10] = (double)L->interval_converged;
+      t[11] = L->a_t; t[12] = L->a_l; t[13] = L->f_l; t[14] = L->g_l; t[15] = L->a_u; t[16] = L->f_u; t[17] = L->g_u;
+      t[18] = L->phi_0; t[19] = L->d_phi_0;
+      for (int i = 0; i < 6; i++) { t[20 + i] = L->p[i]; t[26 + i] = L->x_t[i]; t[32 + i] = L->dir[i]; t[39 + i] = L->g[i]; }
+      t[38] = L->score;
+      t[45] = L->trans_probability; t[46] = L->last_pairs;
+      L->pad1 = 0;
+    }
+    wave_lds_fence();
+    used++;
+  }
+  if (lane == 0) *n_used = used;
+}
+
+// solve6_wave on `count` systems, one after another on the wave
+__global__ __launch_bounds__(64) void ndt_solve6_kernel(const double* __restrict__ Hu21, const double* __restrict__ g6, int count,
+                                                        double* __restrict__ delta6) {
+  __shared__ double s_h[24], s_g[8], s_out[8];
+  const int lane = threadIdx.x;
+  for (int i = 0; i < count; i++) {
+    if (lane < 21) s_h[lane] = Hu21[(size_t)i * 21 + lane];
+    if (lane < 6) s_g[lane] = g6[(size_t)i * 6 + lane];
+    wave_lds_fence();
+    solve6_wave((const LdsDouble*)s_h, (const LdsDouble*)s_g, (LdsDouble*)s_out);
+    wave_lds_fence();
+    if (lane < 6) delta6[(size_t)i * 6 + lane] = s_out[lane];
+    wave_lds_fence();
+  }
+}
+
+__global__ __launch_bounds__(64) void mt_math_kernel(const double* __restrict__ a, const double* __restrict__ b, int count,
+                                                     double* __restrict__ quot, double* __restrict__ root) {
+  for (int i = threadIdx.x; i < count; i += 64) {
+    quot[i] = mt_div(a[i], b[i]);
+    root[i] = mt_sqrt(a[i]);
+  }
+}
+
 }  // namespace
 
 }  // namespace lsr
@@ -1579,6 +1660,74 @@ extern "C" int lsr_debug_guess_pose(const float* guess16, double* p6) {
   lsr::NdtState st;
   lsr::ndt_fill_initial_state(st, guess16, lsr::NdtParamsHost(), 0);
   for (int i = 0; i < 6; i++) p6[i] = st.p[i];
+  return LSR_OK;
+}
+// The controller on prepared sums (ndt_controller_replay_kernel): the initial state as ndt_fill_initial_state leaves it, with p given.
+extern "C" int lsr_debug_ndt_controller_replay(lsr_handle h, const double* p6, double step_size, double trans_eps, int max_iterations,
+                                               int n_points, const double* rows, int n_rows, double* trace, int* n_used) {
+  if (!p6 || !rows || !trace || !n_used || n_rows < 1 || n_rows > lsr::NDT_REPLAY_MAX_ROWS || n_points < 1) {
+    lsr::set_last_error("controller replay: a null pointer, n_rows outside 1 .. LSR_NDT_REPLAY_MAX_ROWS or n_points below 1");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  LSR_CHECK_HANDLE(h);
+  lsr::NdtParamsHost prm;
+  prm.step_size = step_size;
+  prm.trans_eps = trans_eps;
+  prm.max_iterations = max_iterations;
+  lsr::NdtState st;
+  lsr::ndt_fill_initial_state(st, nullptr, prm, n_points);
+  for (int i = 0; i < 6; i++) st.p[i] = st.x_t[i] = p6[i];
+  lsr::DevBuf<double> in, out;
+  lsr::DevBuf<int> used;
+  const size_t n_in = (size_t)n_rows * lsr::NDT_REPLAY_ROW, n_out = (size_t)n_rows * lsr::NDT_REPLAY_TRACE;
+  if (int s = in.reserve(n_in)) return s;
+  if (int s = out.reserve(n_out)) return s;
+  if (int s = used.reserve(1)) return s;
+  LSR_HIP(hipMemcpyAsync(in.p, rows, n_in * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  LSR_HIP(hipMemsetAsync(out.p, 0, n_out * sizeof(double), h->stream));
+  hipLaunchKernelGGL(lsr::ndt_controller_replay_kernel, dim3(1), dim3(64), 0, h->stream, st, in.p, n_rows, out.p, used.p);
+  LSR_HIP(hipGetLastError());
+  LSR_HIP(hipMemcpyAsync(trace, out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipMemcpyAsync(n_used, used.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  return LSR_OK;
+}
+extern "C" int lsr_debug_ndt_solve6(lsr_handle h, const double* Hu21, const double* g6, int count, double* delta6) {
+  if (!Hu21 || !g6 || !delta6 || count < 1 || count > LSR_DEBUG_MAX_COUNT) {
+    lsr::set_last_error("solve6: a null pointer or count outside 1 .. LSR_DEBUG_MAX_COUNT");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  LSR_CHECK_HANDLE(h);
+  const size_t n = (size_t)count;
+  lsr::DevBuf<double> in, out;
+  if (int s = in.reserve(27 * n)) return s;
+  if (int s = out.reserve(6 * n)) return s;
+  double* d_g = in.p + 21 * n;
+  LSR_HIP(hipMemcpyAsync(in.p, Hu21, 21 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  LSR_HIP(hipMemcpyAsync(d_g, g6, 6 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(lsr::ndt_solve6_kernel, dim3(1), dim3(64), 0, h->stream, in.p, d_g, count, out.p);
+  LSR_HIP(hipGetLastError());
+  LSR_HIP(hipMemcpyAsync(delta6, out.p, 6 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  return LSR_OK;
+}
+extern "C" int lsr_debug_mt_math(lsr_handle h, const double* a, const double* b, int count, double* quot, double* root) {
+  if (!a || !b || !quot || !root || count < 1 || count > LSR_DEBUG_MAX_COUNT) {
+    lsr::set_last_error("mt_math: a null pointer or count outside 1 .. LSR_DEBUG_MAX_COUNT");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  LSR_CHECK_HANDLE(h);
+  const size_t n = (size_t)count;
+  lsr::DevBuf<double> in, out;
+  if (int s = in.reserve(2 * n)) return s;
+  if (int s = out.reserve(2 * n)) return s;
+  LSR_HIP(hipMemcpyAsync(in.p, a, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  LSR_HIP(hipMemcpyAsync(in.p + n, b, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(lsr::mt_math_kernel, dim3(1), dim3(64), 0, h->stream, in.p, in.p + n, count, out.p, out.p + n);
+  LSR_HIP(hipGetLastError());
+  LSR_HIP(hipMemcpyAsync(quot, out.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipMemcpyAsync(root, out.p + n, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
   return LSR_OK;
 }
 namespace lsr {

@@ -519,6 +519,13 @@ def test_c_abi_argument_validation_needs_no_device():
     assert lib.lsr_has_converged(null, C.byref(i32)) == -1
     assert lib.lsr_get_fitness_score(null, C.c_double(1.0), C.byref(dbl)) == -1
     assert lib.lsr_align_batch(None, 0, None, None, None) == -1
+    # the controller's inspection entries: pointers and counts first, then the handle (test_ndt_controller_cpu.py has every argument)
+    d6 = (C.c_double * 64)()
+    assert lib.lsr_debug_ndt_controller_replay(null, d6, 0.1, 0.01, 35, 10, d6, 1, d6, C.byref(i32)) == -1
+    assert lib.lsr_debug_ndt_controller_replay(null, d6, 0.1, 0.01, 35, 10, d6, 513, d6, C.byref(i32)) == -1
+    assert lib.lsr_debug_ndt_controller_replay(null, None, 0.1, 0.01, 35, 10, None, 1, None, None) == -1
+    assert lib.lsr_debug_ndt_solve6(null, d6, d6, 1, d6) == -1 and lib.lsr_debug_ndt_solve6(null, None, None, 0, None) == -1
+    assert lib.lsr_debug_mt_math(null, d6, d6, 1, d6, d6) == -1 and lib.lsr_debug_mt_math(null, None, None, 0, None, None) == -1
     h = C.c_void_p()
     assert lib.lsr_create(7, 0, None, C.byref(h)) == -1 and not h.value  # registration_method neither NDT nor GICP
     assert lib.lsr_create(_capi.METHOD_NDT, 0, None, None) == -1
