@@ -1016,6 +1016,45 @@ int lsr_debug_ndt_solve6(lsr_handle h, const double* Hu21, const double* g6, int
 /* quot[i] = a[i] / b[i] and root[i] = sqrt(a[i]) by the line search's fast fp64 division and square root.
  * 1 <= count <= LSR_DEBUG_MAX_COUNT. */
 int lsr_debug_mt_math(lsr_handle h, const double* a, const double* b, int count, double* quot, double* root);
+/* The four entries below inspect the primitives every voxel path stands on (csrc/lsd_sort.hip): the stable LSD radix sort of
+ * (uint32 key, int32 value) pairs, the exclusive int32 scan, and the runs of equal keys of a sorted sequence (run table, float
+ * centroid of every run, run count).  Each is ONE call of the primitive as the library's own paths call it, on host arrays.
+ * Any registration object serves as h: its device and stream are used and nothing else of it.  Every device buffer, the sort's and the
+ * scan's table and the runs' scratch with its host mailbox are the entry's OWN and are released before it returns, so a build pending on
+ * the object is not disturbed and a later lsr_align returns what it would have returned without the call.  The stream is synchronised
+ * before the entry returns.  A null pointer, a size outside 1 .. LSR_DEBUG_SORT_MAX or any other argument outside its range is
+ * LSR_ERR_INVALID_ARGUMENT before the handle is looked at and before anything is allocated or written; then a null handle is.
+ *
+ * What the primitives will launch for n elements, on the host (needs no device).  out[LSR_DEBUG_LSD_PLAN_WORDS]: for the sort of n pairs on
+ * end_bit bits {passes, bits per pass, 64-key steps per wave (8 or 16: workgroups of 2048 or 4096 keys), workgroups, 1 if every
+ * workgroup prefixes the histogram rows itself (the fused scatter) else 0, covered_bits = passes * bits}; for the scan of n ints
+ * {4096-element blocks, 1 if one launch serves (one block) else 0, block sums per thread of the middle launch}; for the runs of n
+ * keys {256-key blocks, block counts per thread of the scanning launch}.  1 <= end_bit <= 32. */
+#define LSR_DEBUG_SORT_MAX (1 << 24)
+#define LSR_DEBUG_LSD_PLAN_WORDS 11
+#define LSR_DEBUG_CANARY_F32_BITS 0x7FC0DEADu
+int lsr_debug_lsd_plan(size_t n, int end_bit, int* out);
+/* One sort.  The pairs come back ordered by the low covered_bits (>= end_bit) bits of the key, equal ones in input order; the bits
+ * above are carried unchanged (the library's callers keep their keys below 2^end_bit).  vals == NULL: the values are 0 .. n - 1.
+ * alias_vals != 0 (needs vals): the sort is handed ONE buffer as its first value side and as that side's spare, as the map filter
+ * does.  *result_in_b: 1 if the sort left its result on its second side (an odd number of passes), else 0; keys_out / vals_out are
+ * copied from the side it names.  The table is filled with 0xFF bytes before the call, as a larger sort before it might have left it. */
+int lsr_debug_sort_pairs_u32(lsr_handle h, const uint32_t* keys, const int32_t* vals, size_t n, int end_bit, int alias_vals,
+                             uint32_t* keys_out, int32_t* vals_out, int* result_in_b);
+/* One exclusive scan: out[i] = in[0] + .. + in[i - 1] in int32.  On the device `in` starts in_shift ints and `out` out_shift ints
+ * (each 0 .. 3) past a 16-byte boundary. */
+int lsr_debug_exclusive_scan_i32(lsr_handle h, const int32_t* in, size_t n, int in_shift, int out_shift, int32_t* out);
+/* The runs of equal keys of keys_sorted[n]: heads counted and scanned (with the count left in device memory too), the run table, the
+ * centroid of every run, then the count read from the host mailbox.  order[n] (each 0 .. n - 1) names the point of every sorted
+ * position in the planes x, y, z, w (w nullable; cw is null exactly when w is).  The run of key `sentinel` gets no centroid;
+ * sentinel_on_device != 0: the kernel reads the sentinel from device memory and is handed ~sentinel by value.
+ * run_key / run_off: n + 1 entries, run r covers the sorted positions [run_off[r], run_off[r + 1]); cx, cy, cz, cw: n entries, one
+ * per run in key order.  Before the launches the device outputs are filled with a canary, 0xFFFFFFFF words in the tables and floats
+ * of the bits LSR_DEBUG_CANARY_F32_BITS (a NaN) in the centroids: what comes back as canary was not written.
+ * *n_runs: the count from the mailbox; *n_runs_dev: the count left in device memory. */
+int lsr_debug_sorted_runs(lsr_handle h, const uint32_t* keys_sorted, const int32_t* order, size_t n, const float* x, const float* y,
+                          const float* z, const float* w, uint32_t sentinel, int sentinel_on_device, uint32_t* run_key, int32_t* run_off,
+                          float* cx, float* cy, float* cz, float* cw, int* n_runs, int* n_runs_dev);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@ ERR_NOT_IMPLEMENTED, ERR_INDEX_OVERFLOW = -6, -7
 ERR_IO = -9
 PCD_ASCII_MAX_LINE_BYTES, PCD_ASCII_MAX_HEADER_BYTES = 60, 256
 NDT_REPLAY_MAX_ROWS, NDT_REPLAY_TRACE, DEBUG_MAX_COUNT = 512, 47, 1 << 20
+DEBUG_SORT_MAX, DEBUG_LSD_PLAN_WORDS, DEBUG_CANARY_F32_BITS = 1 << 24, 11, 0x7FC0DEAD
 (MAX_ITERATIONS, NEIGHBORHOOD, NUM_THREADS, K_CORRESPONDENCES, MAX_INNER_ITERATIONS, RANSAC_ITERATIONS,
  HESSIAN_D1_SIGN, PROFILE, NDT_WORKGROUP, NDT_TABLE_MODE, GRID_BUILDER, WAIT_MODE, NDT_QUAD, _UNASSIGNED_45, VOXEL_FILTER_FORM, NDT_SPLIT, TARGET_PREPARED,
  MAP_ASSEMBLY_FORM) = range(32, 50)
@@ -66,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "lsr_voxel_grid_filter_map", "lsr_assemble_map_filtered", "lsr_save_map_pcd_filtered",
     "lsr_map_window_around", "lsr_crop_map", "lsr_set_input_target_window",
     "lsr_ndt_score_poses", "lsr_pose_lattice_poses", "lsr_select_poses", "lsr_ndt_search_pose",
+    "lsr_debug_lsd_plan", "lsr_debug_sort_pairs_u32", "lsr_debug_exclusive_scan_i32", "lsr_debug_sorted_runs",
 ]
 
 
@@ -258,6 +260,11 @@ def load() -> C.CDLL:
     L.lsr_debug_ndt_controller_replay.argtypes = [vp, dp, C.c_double, C.c_double, C.c_int, C.c_int, dp, C.c_int, dp, C.POINTER(C.c_int)]
     L.lsr_debug_ndt_solve6.argtypes = [vp, dp, dp, C.c_int, dp]
     L.lsr_debug_mt_math.argtypes = [vp, dp, dp, C.c_int, dp, dp]
+    up, cip = C.POINTER(C.c_uint32), C.POINTER(C.c_int)
+    L.lsr_debug_lsd_plan.argtypes = [C.c_size_t, C.c_int, cip]
+    L.lsr_debug_sort_pairs_u32.argtypes = [vp, up, ip, C.c_size_t, C.c_int, C.c_int, up, ip, cip]
+    L.lsr_debug_exclusive_scan_i32.argtypes = [vp, ip, C.c_size_t, C.c_int, C.c_int, ip]
+    L.lsr_debug_sorted_runs.argtypes = [vp, up, ip, C.c_size_t, fp, fp, fp, fp, C.c_uint32, C.c_int, up, ip, fp, fp, fp, fp, cip, cip]
     L.lsr_set_input_source_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_double, C.c_double, C.c_float, C.c_int,
                                            C.POINTER(C.c_size_t)]
     L.lsr_get_source_pc2.argtypes = [vp, vp, C.c_size_t, C.POINTER(Pc2Layout), C.POINTER(C.c_size_t)]

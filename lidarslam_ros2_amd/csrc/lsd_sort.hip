@@ -15,6 +15,7 @@
 // The tail of N1 lives here too: the heads of the runs of equal keys are counted per workgroup, scanned by one workgroup (which
 // also reports the number of runs to the host mailbox), and every head then sums its run — three launches instead of a library's
 // run-length encode + exclusive scan + a publishing launch.
+#include "api_internal.hpp"
 #include "handle.hpp"
 #include "sort.hpp"
 #include "voxel_device.hpp"
@@ -576,4 +577,130 @@ int exclusive_scan_i32_lsd(const int* in, int* out, size_t n, DevBuf<char>& temp
   return LSR_OK;
 }
 
+// What the three primitives will launch for n elements (lsr_debug_lsd_plan): the arithmetic of lsd_plan, sort_pairs_u32_lsd,
+// exclusive_scan_i32_lsd and sorted_runs_begin, read off the same constants.
+static void lsd_debug_plan_words(size_t n, int end_bit, int* out) {
+  const LsdPlan P = lsd_plan(n, end_bit);
+  const size_t scan_blocks = (n + XS_CHUNK - 1) / XS_CHUNK, run_blocks = sorted_runs_blocks(n);
+  out[0] = P.passes; out[1] = P.bits; out[2] = P.steps; out[3] = P.nblk;
+  out[4] = P.nblk <= RS_FUSED_MAX_BLOCKS ? 1 : 0;
+  out[5] = P.passes * P.bits;
+  out[6] = (int)scan_blocks; out[7] = scan_blocks == 1 ? 1 : 0; out[8] = (int)((scan_blocks + 1023) / 1024);
+  out[9] = (int)run_blocks; out[10] = (int)((run_blocks + 1023) / 1024);
+}
+static size_t lsd_debug_table_bytes(size_t n, int end_bit) { return lsd_plan(n, end_bit).table_bytes; }
+
 }  // namespace lsr
+
+// ---- inspection entries of the primitives above (include/lidarslam_reg.h) ----------------------------------------------------
+// Every device buffer, the histogram / block-sum table and (for the runs) the BuildScratch with its mailbox are the entry's own and
+// die with the call; of the handle only the device and the stream are used.
+extern "C" int lsr_debug_lsd_plan(size_t n, int end_bit, int* out) {
+  if (!out || n < 1 || n > (size_t)LSR_DEBUG_SORT_MAX || end_bit < 1 || end_bit > 32) {
+    lsr::set_last_error("lsd plan: a null pointer, n outside 1 .. LSR_DEBUG_SORT_MAX or end_bit outside 1 .. 32");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  lsr::lsd_debug_plan_words(n, end_bit, out);
+  return LSR_OK;
+}
+
+extern "C" int lsr_debug_sort_pairs_u32(lsr_handle h, const uint32_t* keys, const int32_t* vals, size_t n, int end_bit, int alias_vals,
+                                        uint32_t* keys_out, int32_t* vals_out, int* result_in_b) {
+  if (!keys || !keys_out || !vals_out || !result_in_b || n < 1 || n > (size_t)LSR_DEBUG_SORT_MAX || end_bit < 1 || end_bit > 32 ||
+      (alias_vals && !vals)) {
+    lsr::set_last_error("debug sort: a null pointer, n outside 1 .. LSR_DEBUG_SORT_MAX, end_bit outside 1 .. 32 or alias_vals without vals");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  LSR_CHECK_HANDLE(h);
+  lsr::DevBuf<unsigned int> words;   // key_a | key_b | val_a | val_a_buf | val_b
+  lsr::DevBuf<char> temp;
+  const size_t table = lsr::lsd_debug_table_bytes(n, end_bit);
+  if (int s = words.reserve(5 * n)) return s;
+  if (int s = temp.reserve(table)) return s;
+  unsigned int *key_a = words.p, *key_b = key_a + n;
+  int *val_a = (int*)(key_b + n), *val_a_buf = alias_vals ? val_a : val_a + n, *val_b = val_a + 2 * n;
+  LSR_HIP(hipMemsetAsync(words.p, 0xFF, 5 * n * sizeof(unsigned int), h->stream));
+  LSR_HIP(hipMemsetAsync(temp.p, 0xFF, table, h->stream));   // what an earlier, larger sort may have left in a grown table
+  LSR_HIP(hipMemcpyAsync(key_a, keys, n * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
+  if (vals) LSR_HIP(hipMemcpyAsync(val_a, vals, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  bool in_b = false;
+  if (int s = lsr::sort_pairs_u32_lsd(key_a, key_b, vals ? val_a : nullptr, val_a_buf, val_b, n, end_bit, temp, h->stream, &in_b)) return s;
+  LSR_HIP(hipMemcpyAsync(keys_out, in_b ? key_b : key_a, n * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipMemcpyAsync(vals_out, in_b ? val_b : val_a_buf, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  *result_in_b = in_b ? 1 : 0;
+  return LSR_OK;
+}
+
+extern "C" int lsr_debug_exclusive_scan_i32(lsr_handle h, const int32_t* in, size_t n, int in_shift, int out_shift, int32_t* out) {
+  if (!in || !out || n < 1 || n > (size_t)LSR_DEBUG_SORT_MAX || in_shift < 0 || in_shift > 3 || out_shift < 0 || out_shift > 3) {
+    lsr::set_last_error("debug scan: a null pointer, n outside 1 .. LSR_DEBUG_SORT_MAX or a shift outside 0 .. 3");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  LSR_CHECK_HANDLE(h);
+  const size_t side = (n + 4 + 3) & ~(size_t)3;   // a multiple of four ints: both sides start on a 16-byte boundary before the shift
+  lsr::DevBuf<int> buf;
+  lsr::DevBuf<char> temp;
+  const size_t table = ((n + lsr::XS_CHUNK - 1) / lsr::XS_CHUNK) * sizeof(int) + 64;
+  if (int s = buf.reserve(2 * side)) return s;
+  if (int s = temp.reserve(table)) return s;
+  int *d_in = buf.p + in_shift, *d_out = buf.p + side + out_shift;
+  LSR_HIP(hipMemsetAsync(buf.p, 0xFF, 2 * side * sizeof(int), h->stream));
+  LSR_HIP(hipMemsetAsync(temp.p, 0xFF, table, h->stream));
+  LSR_HIP(hipMemcpyAsync(d_in, in, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (int s = lsr::exclusive_scan_i32_lsd(d_in, d_out, n, temp, h->stream)) return s;
+  LSR_HIP(hipMemcpyAsync(out, d_out, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  return LSR_OK;
+}
+
+extern "C" int lsr_debug_sorted_runs(lsr_handle h, const uint32_t* keys_sorted, const int32_t* order, size_t n, const float* x, const float* y,
+                                     const float* z, const float* w, uint32_t sentinel, int sentinel_on_device, uint32_t* run_key,
+                                     int32_t* run_off, float* cx, float* cy, float* cz, float* cw, int* n_runs, int* n_runs_dev) {
+  bool ok = keys_sorted && order && x && y && z && run_key && run_off && cx && cy && cz && n_runs && n_runs_dev && ((w != nullptr) == (cw != nullptr)) &&
+            n >= 1 && n <= (size_t)LSR_DEBUG_SORT_MAX;
+  for (size_t i = 0; ok && i < n; i++) ok = order[i] >= 0 && (size_t)order[i] < n;   // the centroid kernel gathers through it
+  if (!ok) {
+    lsr::set_last_error("debug runs: a null pointer, w without cw (or the reverse), n outside 1 .. LSR_DEBUG_SORT_MAX or order outside 0 .. n - 1");
+    return LSR_ERR_INVALID_ARGUMENT;
+  }
+  LSR_CHECK_HANDLE(h);
+  const size_t nb = lsr::sorted_runs_blocks(n), np = (n + 3) & ~(size_t)3;
+  lsr::BuildScratch sc;
+  lsr::DevBuf<unsigned int> words;   // keys[n] | order[n] | block_heads[nb] | block_base[nb] | run_key[n+1] | run_off[n+1] | total, sentinel
+  lsr::DevBuf<float> planes;         // x y z w | cx cy cz cw, np floats each
+  if (int s = words.reserve(4 * n + 2 * nb + 4)) return s;
+  if (int s = planes.reserve(8 * np)) return s;
+  unsigned int* d_keys = words.p;
+  int *d_order = (int*)(d_keys + n), *d_heads = d_order + n, *d_base = d_heads + nb;
+  unsigned int* d_run_key = (unsigned int*)(d_base + nb);
+  int *d_run_off = (int*)(d_run_key + n + 1), *d_total = d_run_off + n + 1;
+  unsigned int* d_sentinel = (unsigned int*)(d_total + 1);
+  float* d_in[4] = {planes.p, planes.p + np, planes.p + 2 * np, w ? planes.p + 3 * np : nullptr};
+  float* d_c[4] = {planes.p + 4 * np, planes.p + 5 * np, planes.p + 6 * np, cw ? planes.p + 7 * np : nullptr};
+  const float* src[4] = {x, y, z, w};
+  LSR_HIP(hipMemsetAsync(words.p, 0xFF, (4 * n + 2 * nb + 4) * sizeof(unsigned int), h->stream));
+  LSR_HIP(hipMemsetD32Async((hipDeviceptr_t)planes.p, (int)LSR_DEBUG_CANARY_F32_BITS, 8 * np, h->stream));
+  LSR_HIP(hipMemcpyAsync(d_keys, keys_sorted, n * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
+  LSR_HIP(hipMemcpyAsync(d_order, order, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  for (int k = 0; k < 4; k++)
+    if (src[k]) LSR_HIP(hipMemcpyAsync(d_in[k], src[k], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (sentinel_on_device) LSR_HIP(hipMemcpyAsync(d_sentinel, &sentinel, sizeof(sentinel), hipMemcpyHostToDevice, h->stream));
+  unsigned int token = 0;
+  if (int s = lsr::sorted_runs_begin(d_keys, n, d_heads, d_base, sc, h->stream, &token, nullptr, d_total)) return s;
+  if (int s = lsr::sorted_runs_table(d_keys, n, d_base, d_run_key, d_run_off, h->stream)) return s;
+  // with the sentinel on the device the by-value argument is wrong on purpose: the kernel must read the device word
+  if (int s = lsr::sorted_runs_centroids(d_keys, d_order, n, d_base, sentinel_on_device ? ~sentinel : sentinel, d_in[0], d_in[1], d_in[2], d_in[3],
+                                         d_c[0], d_c[1], d_c[2], d_c[3], h->stream, sentinel_on_device ? d_sentinel : nullptr)) return s;
+  int count = -1;
+  if (int s = lsr::sorted_runs_count(sc, h->stream, token, &count)) return s;
+  LSR_HIP(hipMemcpyAsync(run_key, d_run_key, (n + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipMemcpyAsync(run_off, d_run_off, (n + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipMemcpyAsync(n_runs_dev, d_total, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  float* dst[4] = {cx, cy, cz, cw};
+  for (int k = 0; k < 4; k++)
+    if (dst[k]) LSR_HIP(hipMemcpyAsync(dst[k], d_c[k], n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  LSR_HIP(hipStreamSynchronize(h->stream));
+  *n_runs = count;
+  return LSR_OK;
+}

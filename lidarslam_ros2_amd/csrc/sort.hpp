@@ -3,9 +3,14 @@
 
 namespace lsr {
 // ---- hand-written stable LSD radix sort + run finder (lsd_sort.hip) -------------------------------------------------------
-// Sorts n pairs on key bits [0, end_bit) in ceil(end_bit / 11) passes, ping-ponging between (key_a, val_a) and (key_b, val_b);
-// val_a == nullptr: the values are 0..n-1 (no iota pass), val_a_buf then serves as the "a" side from the second pass on.
-// *result_in_b says where the sorted pairs ended up.  temp holds the histogram tables.
+// Sorts n pairs in passes = ceil(end_bit / 11) passes of bits = ceil(end_bit / passes) bits each, ping-ponging between (key_a, val_a)
+// and (key_b, val_b).  The pairs come out ordered by the LOW passes * bits BITS of the key, which is at least end_bit and may be more
+// (end_bit 23: three passes of 8 cover 24; end_bit 32: three of 11 cover all 32), equal ones in input order.  Callers keep their keys
+// below 2^end_bit, where the two readings agree; a key bit between end_bit and passes * bits would be ordered by, and every bit above
+// is carried unchanged and ignored.
+// val_a == nullptr: the values are 0..n-1 (no iota pass), val_a_buf then serves as the "a" side from the second pass on (val_a_buf ==
+// val_a is allowed: the first pass has read val_a before the second writes it).
+// *result_in_b says where the sorted pairs ended up (the "b" side after an odd number of passes).  temp holds the histogram tables.
 struct BuildScratch;
 int sort_pairs_u32_lsd(unsigned int* key_a, unsigned int* key_b, int* val_a, int* val_a_buf, int* val_b, size_t n, int end_bit,
                        DevBuf<char>& temp, hipStream_t stream, bool* result_in_b, bool first_hist_done = false);
@@ -20,7 +25,7 @@ struct SortScratch {
   int *run_off, *nruns;
 };
 int sort_scratch_carve(BuildScratch& sc, size_t n, bool run_table, SortScratch* out);
-// Sorts s.key_in with the values 0..n-1 on bits [0, end_bit): *keys / *order say where the sorted keys and the order ended up.
+// Sorts s.key_in (keys below 2^end_bit, see above) with the values 0..n-1: *keys / *order say where the sorted keys and the order ended up.
 int sort_scratch_run(const SortScratch& s, size_t n, int end_bit, DevBuf<char>& temp, hipStream_t stream, const unsigned int** keys,
                      const int** order, bool first_hist_done = false);
 // The first pass's histogram table as that call will lay it out in temp: digit-major uint16 rows hist[digit * row_pitch + workgroup],

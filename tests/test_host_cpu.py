@@ -526,6 +526,12 @@ def test_c_abi_argument_validation_needs_no_device():
     assert lib.lsr_debug_ndt_controller_replay(null, None, 0.1, 0.01, 35, 10, None, 1, None, None) == -1
     assert lib.lsr_debug_ndt_solve6(null, d6, d6, 1, d6) == -1 and lib.lsr_debug_ndt_solve6(null, None, None, 0, None) == -1
     assert lib.lsr_debug_mt_math(null, d6, d6, 1, d6, d6) == -1 and lib.lsr_debug_mt_math(null, None, None, 0, None, None) == -1
+    # the sort / scan / run inspection entries likewise (test_sort_primitives_cpu.py has every argument)
+    u8, i8, f8 = (C.c_uint32 * 8)(), (C.c_int32 * 8)(), (C.c_float * 8)()
+    assert lib.lsr_debug_sort_pairs_u32(null, u8, i8, 8, 12, 0, u8, i8, C.byref(i32)) == -1
+    assert lib.lsr_debug_exclusive_scan_i32(null, i8, 8, 0, 0, i8) == -1
+    assert lib.lsr_debug_sorted_runs(null, u8, i8, 8, f8, f8, f8, None, 9, 0, u8, i8, f8, f8, f8, None, C.byref(i32), C.byref(i32)) == -1
+    assert lib.lsr_debug_lsd_plan(0, 12, i8) == -1 and lib.lsr_debug_lsd_plan(8, 12, None) == -1
     h = C.c_void_p()
     assert lib.lsr_create(7, 0, None, C.byref(h)) == -1 and not h.value  # registration_method neither NDT nor GICP
     assert lib.lsr_create(_capi.METHOD_NDT, 0, None, None) == -1
