@@ -106,6 +106,9 @@ typedef enum lsr_key {
   LSR_POSE_SEARCH_MS = 23,            /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the scoring launch (the
                                          pose upload and the copy of the scores outside the brackets) of the last lsr_ndt_score_poses /
                                          lsr_ndt_search_pose on this object; else 0 */
+  LSR_SCAN_CONTEXT_BUILD_MS = 24,     /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the descriptor launches
+                                         (staging copies outside the brackets) of the last lsr_scan_context_build on this object; */
+  LSR_SCAN_CONTEXT_MATCH_MS = 25,     /* of the comparison launch of the last lsr_scan_context_match / lsr_search_loop_appearance.  Else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,           /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -554,6 +557,81 @@ typedef struct lsr_loop_edge {
 int lsr_search_loop(lsr_handle h, const lsr_submap* submaps, int num_submaps, size_t stride_bytes, int on_device,
                     const lsr_loop_params* params, lsr_loop_edge* edges, int edge_capacity, int* n_evaluated);
 
+/* ---- loop closure by appearance: Scan Context candidates ------------------ */
+/* searchLoop's candidate rule rests on the drifted odometry: a submap is a candidate only when its STORED position is within range of
+ * the latest one, and it is registered without a guess.  After a long featureless stretch the right keyframe is outside that range
+ * and a wrong one inside it.  These entries pick the candidate and its heading by what the place looks like: a Scan Context descriptor
+ * per keyframe (Kim and Kim, IROS 2018: the highest point of every ring x sector cell of a polar grid around the sensor), every stored
+ * descriptor compared with the latest one at every yaw shift, both on the device.  No reference site exists: the definitions are this
+ * project's (unpinned).  They use integer and single-rounded fp32 operations only — every fp32 product, sum, difference, quotient and
+ * square root below is rounded once, nothing is fused —, so a numpy float32 restatement has the same bits (tests/scan_context_numpy.py).
+ *
+ * Parameters: num_rings R in 1 .. 40, num_sectors S even in 2 .. 120, max_radius L > 0, z_offset (the sensor's height above ground).
+ * Tables, made on the host in double and rounded to float once:
+ *   edge2[k] = (float)((k L / R)^2) for k = 1 .. R-1, L2 = (float)(L L);
+ *   b[k] = ((float)cos(2 pi k / S), (float)sin(2 pi k / S)) for k = 1 .. S/2-1 (the C library's cos and sin).
+ * The descriptor of a cloud (pose-local records, x y z at the layout's offsets), R x S floats, ring-major:
+ *   1. a point with a non-finite coordinate is skipped;
+ *   2. r2 = x x + y y (two products, one sum); a point with r2 >= L2 is skipped;
+ *   3. ring = the number of k in 1 .. R-1 with r2 >= edge2[k];
+ *   4. the point is in the upper half if y > 0 || (y == 0 && x >= 0), and then (x', y') = (x, y); else in the lower half with
+ *      (x', y') = (-x, -y).  sector = (lower ? S/2 : 0) + the number of k in 1 .. S/2-1 with b[k].x y' - b[k].y x' >= 0 (two products,
+ *      one difference).  No angle function is used;
+ *   5. the cell's value is the maximum over its points of max(+0, z + (float)z_offset) (a sum that is not > 0 counts as +0); an empty
+ *      cell is +0.
+ *   The result does not depend on the order of the points: one definition, one set of bits whatever the launch form.
+ * The distance of a query q to a candidate c at shift n pairs query column j with candidate column (j + n) mod S — the candidate sees
+ * the query's scene turned by +n 2 pi / S about z:
+ *   1. column norms nq_j = sqrtf(sum_r q q), nc_j = sqrtf(sum_r c c) and dot_j = sum_r q c: r ascending from 0.0f, product then sum;
+ *   2. a column counts when both norms are > 0; term_j = 1.0f - dot_j / (nq_j nc_j);
+ *   3. d(n) = (sum of the terms, j ascending from 0.0f) / (float)count; no column counts: d(n) = 1.0f;
+ *   4. the distance is the minimum over n, ties to the lowest n; candidates of equal distance rank by ascending index.
+ * The guess: G = M_cand Rz(shift 2 pi / S) M_latest^-1 in fp64 from the two stored poses (the matrices of lsr_search_loop), cast to
+ * float element by element — lsr_align's guess for a source that is the latest cloud moved by its stored pose. */
+#define LSR_SCAN_CONTEXT_MAX_RINGS 40
+#define LSR_SCAN_CONTEXT_MAX_SECTORS 120
+typedef struct lsr_scan_context_params { int32_t num_rings, num_sectors; double max_radius, z_offset; } lsr_scan_context_params;
+/* The two tables.  Host only, no handle.  edge2: R floats — edge2[k-1] for k = 1 .. R-1, then L2; boundaries: S - 2 floats — cos, sin
+ * of k = 1 .. S/2-1 (none for S = 2; the pointer is still required).  LSR_ERR_INVALID_ARGUMENT, outputs untouched: a null pointer, R or S
+ * out of range, S odd, L not > 0 or not finite, z_offset not finite. */
+int lsr_scan_context_tables(const lsr_scan_context_params* params, float* edge2, float* boundaries);
+/* The guess G above -> guess16 (column-major float).  Host only, no handle.  0 <= shift < num_sectors, num_sectors even in 2 .. 120. */
+int lsr_scan_context_guess(const lsr_submap* candidate, const lsr_submap* latest, int shift, int num_sectors, float* guess16);
+/* The descriptors of num_submaps submaps in ONE launch over a device table of them (the shape of lsr_assemble_map): submaps[i].cloud =
+ * n_points records of `layout` (x / y / z at its offsets; the intensity offset is not read), all host pointers (on_device == 0: staged
+ * through the object's upload buffer in bounded pieces) or all HIP device pointers -> out_desc[i R S ..], host or (out_on_device != 0)
+ * device.  A submap without points has an all-zero descriptor.  The cells are unsigned integer maxima on the float bits (the values
+ * are >= +0, where the two orders agree), in LDS per workgroup, merged in the output where a submap is split over workgroups.
+ * The call keeps no state: submaps + k with out_desc + k R S writes the bytes a call over all submaps writes there — a caller appends
+ * one descriptor per new keyframe.  Ordering of device inputs: as for lsr_assemble_map; returns when the descriptors are complete.
+ * LSR_ERR_INVALID_ARGUMENT, outputs untouched: null handle, submaps, layout, params or out_desc; num_submaps <= 0; a layout
+ * lsr_deskew_pc2 refuses; parameters lsr_scan_context_tables refuses; a pointer that is not 4-byte aligned; n_points > 0 without a
+ * cloud.  LSR_ERR_INDEX_OVERFLOW: more than INT32_MAX records in all.  LSR_SCAN_CONTEXT_BUILD_MS reports the launches' time. */
+int lsr_scan_context_build(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* layout, int on_device,
+                           const lsr_scan_context_params* params, float* out_desc, int out_on_device);
+/* nq queries against nc candidates, every pair at every shift, in ONE launch: one workgroup per pair, the candidate in LDS with its
+ * columns doubled, one lane per shift walking columns and rings in the order the definition fixes.  q, c: nq and nc descriptors of
+ * R x S floats, both host or (on_device != 0) both device; dist[iq nc + ic], shift[iq nc + ic]: host.  Brute force over every stored
+ * descriptor is the device's answer to a ring-key tree.  LSR_ERR_INVALID_ARGUMENT, outputs untouched: a null pointer, a count < 1,
+ * refused parameters, q or c not 4-byte aligned; LSR_ERR_INDEX_OVERFLOW: more than INT32_MAX pairs.  LSR_SCAN_CONTEXT_MATCH_MS reports
+ * the launch's time. */
+int lsr_scan_context_match(lsr_handle h, const float* q, int nq, const float* c, int nc, int on_device,
+                           const lsr_scan_context_params* params, float* dist, int32_t* shift);
+/* The loop gate with candidate and heading from appearance and the translation from the pose search.
+ * descriptors: num_descriptors x R x S floats, host or (desc_on_device != 0) device, descriptor i of submap i (lsr_scan_context_build);
+ * the latest one is compared with all of them in one launch.  Candidates: the submaps with latest.distance - distance_i >
+ * loop.distance_loop_closure AND Scan Context distance < sc_distance_threshold, ranked by that distance (ties: lower index).  The range
+ * gate (range_of_searching_loop_closure) is NOT applied: it is the drifted position this entry exists to do without.  The first
+ * max(loop.top_k, 1) candidates (at most edge_capacity) are evaluated one after another on `h`: source and window target exactly as
+ * lsr_search_loop builds them; then, NDT: lsr_ndt_search_pose with `search` around G (a search that keeps nothing leaves G itself as the
+ * final transformation, not converged); GICP: one align with guess G; then getFitnessScore, the threshold and the relative pose
+ * from^-1 (final init), as lsr_search_loop fills them — candidate_distance stays the position distance.  shifts[e] and sc_dist[e] beside
+ * edges[e] (both nullable).  Afterwards `h` holds the first candidate's result and window as its input target, as lsr_search_loop leaves
+ * it.  No candidate: LSR_OK with *n_evaluated = 0.
+ * LSR_ERR_INVALID_ARGUMENT, outputs untouched: what lsr_search_loop refuses; null descriptors or params; num_descriptors !=
+ * num_submaps; Scan Context parameters lsr_scan_context_tables refuses; a threshold that is NaN; NDT with a search top_k outside 1 .. 16.
+ * (Declared below, behind lsr_pose_search_params, which its parameters hold.) */
+
 /* ---- the whole map from its submaps -------------------------------------- */
 /* ScanMatcherComponent::publishMap (scanmatcher_component.cpp:529-552) and the map half of doPoseAdjustment
  * (graph_based_slam_component.cpp:321-368): every submap of a lidarslam_msgs/MapArray is moved by its pose and the records are
@@ -954,6 +1032,18 @@ typedef struct lsr_pose_search_report { int32_t n_candidates, n_kept, winner; in
                                         float refined16[16 * 16]; lsr_result refined[16]; } lsr_pose_search_report;
 int lsr_ndt_search_pose(lsr_handle h, const float* center16, const lsr_pose_search_params* p, float* best16, lsr_result* result,
                         lsr_pose_search_report* report /* nullable */);
+
+/* The appearance loop gate (described with the Scan Context entries above, behind lsr_search_loop). */
+typedef struct lsr_appearance_loop_params {
+  lsr_loop_params loop;
+  lsr_scan_context_params sc;
+  double sc_distance_threshold;
+  lsr_pose_search_params search;
+} lsr_appearance_loop_params;
+int lsr_search_loop_appearance(lsr_handle h, const lsr_submap* submaps, int num_submaps, size_t stride_bytes, int on_device,
+                               const float* descriptors, int num_descriptors, int desc_on_device,
+                               const lsr_appearance_loop_params* params, lsr_loop_edge* edges, int32_t* shifts, float* sc_dist,
+                               int edge_capacity, int* n_evaluated);
 
 /* GICP per-point covariances after setInput*: which = 0 source, 1 target (regularised, as the optimiser uses them);
  * 2 source, 3 target: the k-neighbour sample covariance BEFORE the eigen-regularisation.  cov: n*9 doubles. */

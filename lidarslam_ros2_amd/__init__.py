@@ -5,9 +5,10 @@ getFitnessScore) is implemented here — hand-written HIP kernels for gfx950 beh
 include/lidarslam_reg.h.  See DESIGN.md.
 """
 from .registration import (DIRECT1, DIRECT7, DIRECT26, KDTREE, GeneralizedIterativeClosestPoint, MapWindow,
-                           NormalDistributionsTransform, Registration, align_batch, mapWindowAround, odomGuess, poseLattice, selectPoses,
-                           sensorTransformMatrix)
-from .loop_closure import LoopClosureParams, LoopEdge, SubMap, search_loop
+                           NormalDistributionsTransform, Registration, ScanContextParams, align_batch, mapWindowAround, odomGuess, poseLattice,
+                           scanContextGuess, scanContextTables, selectPoses, sensorTransformMatrix)
+from .loop_closure import (AppearanceLoopEdge, AppearanceLoopParams, LoopClosureParams, LoopEdge, SubMap, search_loop,
+                           search_loop_appearance)
 from .map_array import MapArray
 from .localization import Localizer, LocalizerParams
 from . import pose_graph
@@ -15,4 +16,5 @@ from . import pose_graph
 __all__ = ["Registration", "NormalDistributionsTransform", "GeneralizedIterativeClosestPoint", "align_batch",
            "odomGuess", "sensorTransformMatrix", "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray", "pose_graph",
            "MapWindow", "mapWindowAround", "Localizer", "LocalizerParams", "poseLattice", "selectPoses",
-           "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]
+           "ScanContextParams", "scanContextTables", "scanContextGuess", "AppearanceLoopParams", "AppearanceLoopEdge",
+           "search_loop_appearance", "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]

@@ -32,6 +32,8 @@ MAP_WINDOW_MS = 22
 MAP_WINDOW_CELL_LIMIT = 1 << 24
 POSE_SEARCH_MS = 23
 POSE_SEARCH_MAX_POSES, POSE_SEARCH_MAX_KEPT = 1 << 20, 16
+SCAN_CONTEXT_BUILD_MS, SCAN_CONTEXT_MATCH_MS = 24, 25
+SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS = 40, 120
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2           # lsr_pcd_data
 PCD_DATA_KINDS = {"ascii": PCD_ASCII, "binary": PCD_BINARY, "binary_compressed": PCD_BINARY_COMPRESSED}
 PCD_LZF_CHUNK_BYTES = 4096
@@ -67,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "lsr_voxel_grid_filter_map", "lsr_assemble_map_filtered", "lsr_save_map_pcd_filtered",
     "lsr_map_window_around", "lsr_crop_map", "lsr_set_input_target_window",
     "lsr_ndt_score_poses", "lsr_pose_lattice_poses", "lsr_select_poses", "lsr_ndt_search_pose",
+    "lsr_scan_context_tables", "lsr_scan_context_guess", "lsr_scan_context_build", "lsr_scan_context_match", "lsr_search_loop_appearance",
     "lsr_debug_lsd_plan", "lsr_debug_sort_pairs_u32", "lsr_debug_exclusive_scan_i32", "lsr_debug_sorted_runs",
 ]
 
@@ -135,6 +138,14 @@ class PoseSearchParams(C.Structure):
 class PoseSearchReport(C.Structure):
     _fields_ = [("n_candidates", C.c_int32), ("n_kept", C.c_int32), ("winner", C.c_int32), ("kept", C.c_int32 * 16),
                 ("coarse_score", C.c_double * 16), ("refined16", C.c_float * 256), ("refined", Result * 16)]
+
+
+class ScanContextParams(C.Structure):
+    _fields_ = [("num_rings", C.c_int32), ("num_sectors", C.c_int32), ("max_radius", C.c_double), ("z_offset", C.c_double)]
+
+
+class AppearanceLoopParams(C.Structure):
+    _fields_ = [("loop", LoopParams), ("sc", ScanContextParams), ("sc_distance_threshold", C.c_double), ("search", PoseSearchParams)]
 
 
 class PcdInfo(C.Structure):
@@ -237,6 +248,12 @@ def load() -> C.CDLL:
     L.lsr_pose_lattice_poses.argtypes = [fp, C.POINTER(PoseLattice), fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lsr_select_poses.argtypes = [dp, fp, C.c_size_t, C.c_int, C.c_double, C.c_double, ip, C.POINTER(C.c_int)]
     L.lsr_ndt_search_pose.argtypes = [vp, fp, C.POINTER(PoseSearchParams), fp, C.POINTER(Result), C.POINTER(PoseSearchReport)]
+    L.lsr_scan_context_tables.argtypes = [C.POINTER(ScanContextParams), fp, fp]
+    L.lsr_scan_context_guess.argtypes = [C.POINTER(SubMap), C.POINTER(SubMap), C.c_int, C.c_int, fp]
+    L.lsr_scan_context_build.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, C.POINTER(ScanContextParams), vp, C.c_int]
+    L.lsr_scan_context_match.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(ScanContextParams), fp, ip]
+    L.lsr_search_loop_appearance.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.c_size_t, C.c_int, vp, C.c_int, C.c_int,
+                                             C.POINTER(AppearanceLoopParams), C.POINTER(LoopEdge), ip, fp, C.c_int, ip]
     L.lsr_parse_pcd_header.argtypes = [vp, C.c_size_t, C.POINTER(PcdInfo)]
     L.lsr_decode_pcd.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_load_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]

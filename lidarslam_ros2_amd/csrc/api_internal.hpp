@@ -1,5 +1,5 @@
 // What the host units behind the C ABI share (capi.hip, handle_ops.hip, ndt_align.hip, inputs.hip, sensor_frame.hip, loop_search.hip,
-// map_output.hip, pcd_input.hip and the C ABI at the bottom of deskew.hip and map_filter.hip): the handle check every entry
+// map_output.hip, pcd_input.hip and the C ABI at the bottom of deskew.hip, map_filter.hip and scan_context.hip): the handle check every entry
 // starts with, the argument
 // checks of record_args.hpp reported through set_last_error, the staging of host records on their way in and out, and the functions
 // that cross a unit boundary.

@@ -172,6 +172,8 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
       *v = h->map_filter.ms[key - LSR_MAP_FILTER_BBOX_MS]; return LSR_OK;
     case LSR_MAP_WINDOW_MS: *v = h->map_window.ms; return LSR_OK;
     case LSR_POSE_SEARCH_MS: *v = h->pose_search.ms; return LSR_OK;
+    case LSR_SCAN_CONTEXT_BUILD_MS: *v = h->scan_context.build_ms; return LSR_OK;
+    case LSR_SCAN_CONTEXT_MATCH_MS: *v = h->scan_context.match_ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }

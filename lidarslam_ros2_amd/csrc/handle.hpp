@@ -12,6 +12,7 @@
 #include "pcd_text.hpp"
 #include "pose_graph.hpp"
 #include "pose_search.hpp"
+#include "scan_context.hpp"
 
 namespace lsr {
 // A deferred stream dependency (round 6): the group launches of a candidate set run on the FIRST member's stream; instead of making
@@ -110,6 +111,8 @@ struct lsr_handle_s {
   lsr::MapWindowState map_window;   // lsr_crop_map / lsr_set_input_target_window (csrc/map_window.hip): scratch, kept between calls
 
   lsr::PoseSearchState pose_search;   // lsr_ndt_score_poses / lsr_ndt_search_pose (csrc/pose_search.hip): pose and score buffers, kept between calls
+
+  lsr::ScanContextState scan_context;   // lsr_scan_context_build / _match / lsr_search_loop_appearance (csrc/scan_context.hip): tables and staged descriptors, kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1) and lsr_ndt_search_pose: one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

@@ -18,7 +18,7 @@ import numpy as np
 from . import _capi
 from .loop_closure import SubMap
 from .posemath import matrix_from_pose, quaternion_from_matrix
-from .registration import PC2_XYZI, _is_torch_cuda
+from .registration import PC2_XYZI, ScanContextParams, _is_torch_cuda
 
 
 def _as_float_records(records, point_step: int):
@@ -46,6 +46,9 @@ class MapArray:
         self._published_submaps = 0   # submaps it holds
         self._published_records = 0   # records it holds
         self._first_record = [0]
+        self._sc_table = None         # resident descriptor table of scan_contexts: (capacity, R, S) float32
+        self._sc_count = 0            # submaps it holds
+        self._sc_params = None
 
     def __len__(self) -> int:
         return len(self.submaps)
@@ -132,6 +135,36 @@ class MapArray:
             self._published = self._empty(step, False, reg)
         n = self._published_records
         return self._published[: n * step].reshape(n, step), np.array(self._first_record, np.int64)
+
+    def scan_contexts(self, reg, params: ScanContextParams = ScanContextParams()):
+        """The Scan Context descriptor of every submap, for loop_closure.search_loop_appearance: a resident table (on the device when
+        the submaps are) that grows geometrically and is extended by the submaps added since the last call only — a descriptor depends
+        on its own cloud alone.  Other `params` than last time start the table again.  -> (n, R, S) float32, a view of that table,
+        valid until the next call."""
+        params = ScanContextParams(*params)
+        R, S = int(params.num_rings), int(params.num_sectors)
+        if self._sc_params != params:
+            self._sc_table, self._sc_count, self._sc_params = None, 0, params
+        n = len(self.submaps)
+        if n > self._sc_count:
+            cap = 0 if self._sc_table is None else int(self._sc_table.shape[0])
+            if n > cap:
+                on_device = any(_is_torch_cuda(s.cloud) for s in self.submaps)
+                grown = self._empty(max(n, 2 * cap, 1) * R * S * 4, on_device, reg)
+                if on_device:
+                    import torch
+
+                    grown = grown.view(torch.float32).reshape(-1, R, S)
+                else:
+                    grown = grown.view(np.float32).reshape(-1, R, S)
+                if self._sc_count:
+                    grown[: self._sc_count] = self._sc_table[: self._sc_count]
+                self._sc_table = grown
+            reg.scanContext(self.submaps[self._sc_count:], params, self.layout, self._sc_table[self._sc_count:])
+            self._sc_count = n
+        if self._sc_table is None:
+            return np.zeros((0, R, S), np.float32)
+        return self._sc_table[:n]
 
     @staticmethod
     def _empty(nbytes: int, on_device: bool, reg):

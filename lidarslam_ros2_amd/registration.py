@@ -84,6 +84,47 @@ def selectPoses(score, poses, top_k: int = 16, min_sep_m: float = 0.9, min_sep_r
     return kept[:n.value].copy()
 
 
+class ScanContextParams(NamedTuple):
+    """lsr_scan_context_params: num_rings x num_sectors cells out to max_radius [m]; z_offset = the sensor's height above ground."""
+    num_rings: int = 20
+    num_sectors: int = 60
+    max_radius: float = 80.0
+    z_offset: float = 2.0
+
+    def struct(self) -> "capi.ScanContextParams":
+        return capi.ScanContextParams(int(self.num_rings), int(self.num_sectors), float(self.max_radius), float(self.z_offset))
+
+
+def scanContextTables(params: ScanContextParams = ScanContextParams()):
+    """The two tables of the descriptor through lsr_scan_context_tables; needs no device.  -> (edge2 (R,) float32: the squared ring
+    edges k = 1 .. R-1, then L2; boundaries (S/2 - 1, 2) float32: cos, sin of 2 pi k / S for k = 1 .. S/2-1)."""
+    R, S = int(params.num_rings), int(params.num_sectors)
+    edge2 = np.zeros(max(R, 1), np.float32)
+    b = np.zeros(max(S, 2), np.float32)
+    cp = params.struct()
+    fp = C.POINTER(C.c_float)
+    capi.check(capi.load().lsr_scan_context_tables(C.byref(cp), edge2.ctypes.data_as(fp), b.ctypes.data_as(fp)), "scanContextTables")
+    return edge2[:R].copy(), b[: S - 2].reshape(-1, 2).copy()
+
+
+def _pose_submap(sm) -> "capi.SubMap":
+    s = capi.SubMap()
+    s.position[:] = [float(v) for v in sm.position]
+    s.orientation[:] = [float(v) for v in sm.orientation]
+    s.distance = float(getattr(sm, "distance", 0.0))
+    return s
+
+
+def scanContextGuess(candidate, latest, shift: int, num_sectors: int = 60) -> np.ndarray:
+    """lsr_align's guess from appearance through lsr_scan_context_guess: M_cand Rz(shift 2 pi / S) M_latest^-1 in fp64 from the two
+    stored poses (objects with `position` and `orientation`), cast to float.  Needs no device.  -> (4, 4) fp32."""
+    a, b = _pose_submap(candidate), _pose_submap(latest)
+    g = np.zeros(16, np.float32)
+    capi.check(capi.load().lsr_scan_context_guess(C.byref(a), C.byref(b), int(shift), int(num_sectors), g.ctypes.data_as(C.POINTER(C.c_float))),
+               "scanContextGuess")
+    return _col16_to_mat(g)
+
+
 def _window_struct(window) -> capi.MapWindow:
     leaf, lo, hi = window
     return capi.MapWindow(float(leaf), (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]))
@@ -639,6 +680,88 @@ class Registration:
         """The bits of the largest leaf index of the last map filter on this object (LSR_MAP_FILTER_KEY_BITS); above 32 the index was
         sorted as two words; 0 = none yet."""
         return self._geti(capi.MAP_FILTER_KEY_BITS)
+
+    # -- Scan Context (SURVEY.md 8f N10) -----------------------------------------------------------------
+    def scanContext(self, submaps, params: "ScanContextParams" = None, layout=PC2_XYZI, out=None):
+        """The Scan Context descriptor of every submap through lsr_scan_context_build, one launch over all of them.  `submaps`:
+        objects with `cloud` (record buffers of `layout`, pose-local; all numpy arrays or all CUDA tensors), as assembleMap takes
+        them.  `out`: None = a new buffer (a CUDA tensor when the clouds are), or the float32 buffer to write — a view of a resident
+        table advanced by k descriptors appends.  -> (n, num_rings, num_sectors) float32."""
+        params = params or ScanContextParams()
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("scanContext needs at least one submap")
+        li = self._layout(*layout)
+        arr, keep, residency, _, _ = self._submap_table(submaps, None, int(layout[0]))
+        R, S = int(params.num_rings), int(params.num_sectors)
+        if out is None:
+            if residency:
+                import torch
+
+                out = torch.empty((n, R, S), dtype=torch.float32, device=torch.device("cuda", self._device))
+            else:
+                out = np.zeros((n, R, S), np.float32)
+        out_dev = _is_torch_cuda(out)
+        if out_dev:
+            import torch
+
+            if not out.is_contiguous() or out.dtype != torch.float32 or out.numel() < n * R * S:
+                raise ValueError("out must be a contiguous float32 buffer of n x num_rings x num_sectors")
+            optr, flat = out.data_ptr(), out.view(-1)
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable
+                    and out.size >= n * R * S):
+                raise ValueError("out must be a writeable contiguous float32 buffer of n x num_rings x num_sectors")
+            optr, flat = out.ctypes.data, out.reshape(-1)
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        if out_dev:
+            _order_after_torch(self, out)
+        cp = params.struct()
+        capi.check(self._lib.lsr_scan_context_build(self._h, arr, n, C.byref(li), 1 if residency else 0, C.byref(cp), C.c_void_p(optr),
+                                                    1 if out_dev else 0), "scanContext")
+        return flat[: n * R * S].reshape(n, R, S)
+
+    def matchScanContext(self, q, c, params: "ScanContextParams" = None):
+        """Every query descriptor against every candidate descriptor at every yaw shift through lsr_scan_context_match, one launch.
+        q: (nq, R, S) or (R, S); c: (nc, R, S) or (R, S); both numpy arrays or both CUDA tensors, float32.
+        -> (dist (nq, nc) float32, shift (nq, nc) int32): the smallest distance over the shifts and the lowest shift that has it."""
+        params = params or ScanContextParams()
+        cells = int(params.num_rings) * int(params.num_sectors)
+        dev = _is_torch_cuda(q)
+        if dev != _is_torch_cuda(c):
+            raise ValueError("q and c must share residency (host/device)")
+        holders = []
+        ptrs, counts = [], []
+        for d in (q, c):
+            if dev:
+                import torch
+
+                t = d if d.is_contiguous() else d.contiguous()
+                if t.dtype != torch.float32 or t.numel() == 0 or t.numel() % cells:
+                    raise ValueError("descriptors must be float32 of shape (n, num_rings, num_sectors)")
+                ptrs.append(t.data_ptr()); counts.append(t.numel() // cells)
+            else:
+                t = np.ascontiguousarray(d, np.float32)
+                if t.size == 0 or t.size % cells:
+                    raise ValueError("descriptors must be float32 of shape (n, num_rings, num_sectors)")
+                ptrs.append(t.ctypes.data); counts.append(t.size // cells)
+            holders.append(t)
+        if dev:
+            _order_after_torch(self, holders[-1])
+        nq, nc = counts
+        dist, shift = np.zeros((nq, nc), np.float32), np.zeros((nq, nc), np.int32)
+        cp = params.struct()
+        capi.check(self._lib.lsr_scan_context_match(self._h, C.c_void_p(ptrs[0]), nq, C.c_void_p(ptrs[1]), nc, 1 if dev else 0, C.byref(cp),
+                                                    dist.ctypes.data_as(C.POINTER(C.c_float)), shift.ctypes.data_as(C.POINTER(C.c_int32))),
+                   "matchScanContext")
+        return dist, shift
+
+    def scanContextMs(self):
+        """hipEvent time [ms] of the launches of the last scanContext and of the last matchScanContext / search_loop_appearance
+        comparison on this object (setProfiling(True)), else 0.  -> (build, match)"""
+        return self._getf(capi.SCAN_CONTEXT_BUILD_MS), self._getf(capi.SCAN_CONTEXT_MATCH_MS)
 
     def _submap_table(self, submaps, poses, in_step: int):
         """The lsr_submap array of assembleMap / saveMapPCDFileASCII -> (array, keepalives, on_device, total records, column-major
