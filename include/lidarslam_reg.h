@@ -109,6 +109,11 @@ typedef enum lsr_key {
   LSR_SCAN_CONTEXT_BUILD_MS = 24,     /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the descriptor launches
                                          (staging copies outside the brackets) of the last lsr_scan_context_build on this object; */
   LSR_SCAN_CONTEXT_MATCH_MS = 25,     /* of the comparison launch of the last lsr_scan_context_match / lsr_search_loop_appearance.  Else 0 */
+  LSR_DEPTH_IMAGES_MS = 26,           /* read-only (lsr_get_f64): with LSR_PROFILE = 1, the hipEvent time [ms] of the image launches (build
+                                         and erosion; the fill and the staging copies outside the brackets) of the last
+                                         lsr_depth_images_build on this object; */
+  LSR_VISIBILITY_MS = 27,             /* of the votes launch of the last lsr_visibility_votes, or of the votes and the three launches of
+                                         the compaction (count, scan, write) of the last lsr_assemble_map_static.  Else 0 */
   /* int-valued (lsr_set_i32 / lsr_get_i32) */
   LSR_MAX_ITERATIONS = 32,           /* setMaximumIterations               graph_based_slam_component.cpp:66,77 */
   LSR_NEIGHBORHOOD = 33,              /* setNeighborhoodSearchMethod        scanmatcher_component.cpp:110 */
@@ -169,6 +174,9 @@ typedef enum lsr_key {
   LSR_MAP_FILTER_KEY_BITS = 55,       /* read-only (lsr_get_i32): the bits of the largest leaf index of the last lsr_voxel_grid_filter_map /
                                          lsr_assemble_map_filtered / lsr_save_map_pcd_filtered on this object (0 before the first, and
                                          after a cloud without a finite point); above 32 the index was sorted as two words */
+  LSR_VISIBILITY_PIECE_BYTES = 56,    /* bytes per staging piece of HOST clouds in lsr_depth_images_build / lsr_visibility_votes /
+                                         lsr_assemble_map_static's votes (256 .. 1 << 30, default 1 << 26): the table of submaps is walked
+                                         one launch per piece, a long submap cut.  The images and the votes do not depend on it */
   LSR_GICP_SOLVER = 51                /* GICP inner optimiser (lsr_gicp_solver): LSR_GICP_GAUSS_NEWTON (default) or LSR_GICP_BFGS, the
                                          reference's own schedule (PCL's port of GSL vector_bfgs2: Fletcher line search, memoryless
                                          direction update, |g| < 1e-2 / max_inner_iterations / no progress).  Per object, no environment
@@ -660,6 +668,87 @@ int lsr_scan_context_match(lsr_handle h, const float* q, int nq, const float* c,
 int lsr_assemble_map(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
                      const double* poses16 /* nullable */, void* out_data, size_t capacity_points,
                      const lsr_pc2_layout* out_layout, int out_on_device, size_t* first_record /* nullable */, size_t* n_out);
+
+/* ---- moving objects out of the map: visibility votes ---------------------- */
+/* lsr_assemble_map keeps every record of every keyframe: a car that drove ahead of the vehicle is in the map once per keyframe that saw
+ * it, a streak along the lane, and the voxel filter thins the streak and keeps it.  A keyframe whose beam reached a surface BEHIND a
+ * stored point saw through that point: the point was not there at that time.  These entries make that z-buffer test per (record,
+ * neighbouring keyframe) on the device and assemble the map of the records with fewer than min_votes such votes against them.  No
+ * reference site exists: the definition is this project's (unpinned).  It uses integer and single-rounded fp32 operations only — every
+ * fp32 product, sum, difference, quotient and square root below is rounded once, nothing is fused —, so a numpy float32 restatement has
+ * the same bits (tests/map_visibility_numpy.py).
+ *
+ * Parameters (defaults of the bindings in brackets): face_width W [128] even in 8 .. 1024, the columns per 90 degrees; height H [32] in
+ * 4 .. 512, the rows; max_tan_elevation T [tan 30 deg] > 0; min_range [0.5] < max_range [80], both finite, max_range > 0; margin [0.5]
+ * >= 0, metres; keyframe_range [30] > 0; max_neighbours [32] in 1 .. 64; min_votes [2] >= 1; sensor_origin [0, 0, 0], the lidar in the
+ * keyframe's frame.  Constants, made on the host in double and rounded to float once: hw = (float)(W / 2), Tf = (float)T,
+ * rs = (float)(H / (2 T)), and the floats of min_range, max_range, margin and the origin.
+ *   1. The pixel of a sensor-centred point (x, y, z).  The depth image is H rows x 4 W columns: the four side faces of a cube laid side
+ *      by side, with column wrap.  A point with a non-finite coordinate has no pixel.  d = max(|x|, |y|); d == 0: no pixel.
+ *      |x| >= |y|: face = (x > 0 ? 0 : 2), u = y / x; else face = (y > 0 ? 1 : 3), u = -x / y — azimuth ascends with the column across
+ *      all four faces.  r = sqrtf((x x + y y) + z z); r < min_range or r >= max_range: no pixel.  v = z / d,
+ *      rowf = floorf((v + Tf) * rs), the row test made in float: rowf < 0, rowf >= H or a row that is not finite: no pixel.
+ *      col = face W + min(W - 1, (int)floorf((u + 1.0f) * hw)).  No angle function is used.
+ *   2. The depth image of a keyframe: D[row][col] = the minimum of r over the keyframe's own records, sensor_origin subtracted
+ *      component-wise before step 1, that have a pixel; an empty pixel is +inf (bits 0x7f800000).  An unsigned integer minimum on the
+ *      float bits (r >= +0, where the two orders agree): the image does not depend on point order or launch form.
+ *   3. The eroded image: E[row][col] = the minimum of D over rows row-1 .. row+1 clamped to 0 .. H-1 and columns col-1 .. col+1 modulo
+ *      4 W.  This is what is compared against: a point counts as seen through only when every beam around its direction went further.
+ *   4. Neighbours and transforms (host, fp64).  The poses are poses16 when given, else the stored ones (the matrices lsr_assemble_map
+ *      uses).  N(i) = the keyframes k != i with |t_k - t_i| <= keyframe_range, of which the max_neighbours nearest are kept (ties to the
+ *      lower index), listed in ascending k.  T_ki = M_k^-1 M_i with the rigid inverse (R^T, -R^T t); its first three rows cast to float
+ *      element by element.
+ *   5. The votes of record p of keyframe i.  For each k in N(i): q = ((m00 x + m01 y) + m02 z) + m03 row by row with T_ki's floats (the
+ *      expression of lsr_assemble_map), sensor_origin subtracted, the pixel by step 1; one vote when the pixel exists, E_k there is
+ *      finite and r + margin < E_k[pixel] (one sum, one compare).  A record without a pixel anywhere has 0 votes and is kept.
+ *   6. The static map: the records of lsr_assemble_map (same poses, same bytes per record) whose votes are below min_votes, in input
+ *      order; first_record indexes the kept records. */
+#define LSR_VISIBILITY_MAX_FACE_WIDTH 1024
+#define LSR_VISIBILITY_MAX_HEIGHT 512
+#define LSR_VISIBILITY_MAX_NEIGHBOURS 64
+typedef struct lsr_visibility_params {
+  int32_t face_width, height;
+  double max_tan_elevation, min_range, max_range, margin, keyframe_range;
+  int32_t max_neighbours, min_votes;
+  double sensor_origin[3];
+} lsr_visibility_params;
+/* Step 4.  Host only, no handle.  The clouds of the submaps are not looked at.  first_pair: num_submaps + 1 entries — the pairs of
+ * keyframe i are [first_pair[i], first_pair[i+1]); other[p] = k; rel12[12 p ..] = the first three rows of T_ki, row-major.  *n_pairs =
+ * the number of pairs (at most num_submaps x min(max_neighbours, num_submaps - 1)); more than capacity_pairs of them:
+ * LSR_ERR_INVALID_ARGUMENT with *n_pairs set and the tables untouched.  LSR_ERR_INVALID_ARGUMENT, outputs untouched: a null pointer
+ * (poses16 may be null), num_submaps < 1, a parameter outside the ranges above. */
+int lsr_visibility_pairs(const lsr_submap* submaps, int num_submaps, const double* poses16 /* nullable */,
+                         const lsr_visibility_params* params, int32_t* first_pair, int32_t* other, float* rel12, size_t capacity_pairs,
+                         size_t* n_pairs);
+/* Steps 1 - 3: the depth image (eroded == 0: D, else E) of num_submaps submaps in ONE launch over a device table of them, the erosion in
+ * one more over all images.  submaps, layout, on_device: as for lsr_scan_context_build -> out_images[i H 4W ..], host or
+ * (out_on_device != 0) device.  A pixel is lowered by an unsigned minimum straight in the image: at 16 384 pixels for the few ten
+ * thousand records of a keyframe a copy in LDS costs more to clear and merge than the atomics it saves, so there is one launch form.
+ * The call keeps no state: submaps + k with out_images advanced by k images writes the bytes a call over all submaps writes there —
+ * a caller appends one image per new keyframe.  LSR_ERR_INVALID_ARGUMENT, outputs untouched: what lsr_scan_context_build refuses, with
+ * these parameters.  LSR_ERR_INDEX_OVERFLOW: more than INT32_MAX records in all.  LSR_DEPTH_IMAGES_MS reports the launches' time. */
+int lsr_depth_images_build(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* layout, int on_device,
+                           const lsr_visibility_params* params, int eroded, float* out_images, int out_on_device);
+/* Step 5: votes[g] for every record in assembly order (g = first_record[i] + p), int32, host or (votes_on_device != 0) device; one lane
+ * per record, a workgroup never straddles a submap (the pair list and the 12 floats of a pair are uniform loads, the pixel of E the one
+ * gather per pair).  images: the num_submaps ERODED images, host or (images_on_device != 0) device.  first_record (nullable,
+ * num_submaps + 1 entries) and *n_records as lsr_assemble_map fills them.  Refusals as lsr_depth_images_build; null images, votes or
+ * n_records too.  LSR_VISIBILITY_MS reports the launch's time. */
+int lsr_visibility_votes(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* layout, int on_device,
+                         const double* poses16 /* nullable */, const float* images, int images_on_device,
+                         const lsr_visibility_params* params, int32_t* votes, int votes_on_device, size_t* first_record /* nullable */,
+                         size_t* n_records);
+/* Step 6.  lsr_assemble_map's arguments and rules, plus the eroded images and the parameters: the votes, the raw map in a buffer kept on
+ * the object, then flags -> scan -> write in input order (the scan and the ranking of lsr_crop_map; one host wait, for the count).
+ * *n_out = the records kept, *n_removed = the records left out; first_record indexes the kept records.  out_data == NULL: only the
+ * counts and first_record are set (capacity_points is ignored).  capacity_points below the count: LSR_ERR_INVALID_ARGUMENT, outputs
+ * untouched.  num_submaps == 1, or a pair table that is empty, gives lsr_assemble_map's bytes.  LSR_VISIBILITY_MS reports the votes and
+ * the three launches of the compaction. */
+int lsr_assemble_map_static(lsr_handle h, const lsr_submap* submaps, int num_submaps, const lsr_pc2_layout* in_layout, int on_device,
+                            const double* poses16 /* nullable */, const float* images, int images_on_device,
+                            const lsr_visibility_params* params, void* out_data, size_t capacity_points,
+                            const lsr_pc2_layout* out_layout, int out_on_device, size_t* first_record /* nullable */, size_t* n_out,
+                            size_t* n_removed);
 
 /* ---- map.pcd -------------------------------------------------------- */
 /* pcl::io::savePCDFileASCII("map.pcd", *map_ptr) at the end of doPoseAdjustment (graph_based_slam_component.cpp:369, "too heavy"; reached

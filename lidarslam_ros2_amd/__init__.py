@@ -6,7 +6,7 @@ include/lidarslam_reg.h.  See DESIGN.md.
 """
 from .registration import (DIRECT1, DIRECT7, DIRECT26, KDTREE, GeneralizedIterativeClosestPoint, MapWindow,
                            NormalDistributionsTransform, Registration, ScanContextParams, align_batch, mapWindowAround, odomGuess, poseLattice,
-                           scanContextGuess, scanContextTables, selectPoses, sensorTransformMatrix)
+                           scanContextGuess, scanContextTables, selectPoses, sensorTransformMatrix, VisibilityParams, visibilityPairs)
 from .loop_closure import (AppearanceLoopEdge, AppearanceLoopParams, LoopClosureParams, LoopEdge, SubMap, search_loop,
                            search_loop_appearance)
 from .map_array import MapArray
@@ -17,4 +17,4 @@ __all__ = ["Registration", "NormalDistributionsTransform", "GeneralizedIterative
            "odomGuess", "sensorTransformMatrix", "SubMap", "LoopClosureParams", "LoopEdge", "search_loop", "MapArray", "pose_graph",
            "MapWindow", "mapWindowAround", "Localizer", "LocalizerParams", "poseLattice", "selectPoses",
            "ScanContextParams", "scanContextTables", "scanContextGuess", "AppearanceLoopParams", "AppearanceLoopEdge",
-           "search_loop_appearance", "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]
+           "search_loop_appearance", "VisibilityParams", "visibilityPairs", "DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"]

@@ -34,6 +34,9 @@ POSE_SEARCH_MS = 23
 POSE_SEARCH_MAX_POSES, POSE_SEARCH_MAX_KEPT = 1 << 20, 16
 SCAN_CONTEXT_BUILD_MS, SCAN_CONTEXT_MATCH_MS = 24, 25
 SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_SECTORS = 40, 120
+DEPTH_IMAGES_MS, VISIBILITY_MS = 26, 27
+VISIBILITY_PIECE_BYTES = 56
+VISIBILITY_MAX_FACE_WIDTH, VISIBILITY_MAX_HEIGHT, VISIBILITY_MAX_NEIGHBOURS = 1024, 512, 64
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2           # lsr_pcd_data
 PCD_DATA_KINDS = {"ascii": PCD_ASCII, "binary": PCD_BINARY, "binary_compressed": PCD_BINARY_COMPRESSED}
 PCD_LZF_CHUNK_BYTES = 4096
@@ -70,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "lsr_map_window_around", "lsr_crop_map", "lsr_set_input_target_window",
     "lsr_ndt_score_poses", "lsr_pose_lattice_poses", "lsr_select_poses", "lsr_ndt_search_pose",
     "lsr_scan_context_tables", "lsr_scan_context_guess", "lsr_scan_context_build", "lsr_scan_context_match", "lsr_search_loop_appearance",
+    "lsr_visibility_pairs", "lsr_depth_images_build", "lsr_visibility_votes", "lsr_assemble_map_static",
     "lsr_debug_lsd_plan", "lsr_debug_sort_pairs_u32", "lsr_debug_exclusive_scan_i32", "lsr_debug_sorted_runs",
 ]
 
@@ -142,6 +146,12 @@ class PoseSearchReport(C.Structure):
 
 class ScanContextParams(C.Structure):
     _fields_ = [("num_rings", C.c_int32), ("num_sectors", C.c_int32), ("max_radius", C.c_double), ("z_offset", C.c_double)]
+
+
+class VisibilityParams(C.Structure):
+    _fields_ = [("face_width", C.c_int32), ("height", C.c_int32), ("max_tan_elevation", C.c_double), ("min_range", C.c_double),
+                ("max_range", C.c_double), ("margin", C.c_double), ("keyframe_range", C.c_double), ("max_neighbours", C.c_int32),
+                ("min_votes", C.c_int32), ("sensor_origin", C.c_double * 3)]
 
 
 class AppearanceLoopParams(C.Structure):
@@ -254,6 +264,14 @@ def load() -> C.CDLL:
     L.lsr_scan_context_match.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(ScanContextParams), fp, ip]
     L.lsr_search_loop_appearance.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.c_size_t, C.c_int, vp, C.c_int, C.c_int,
                                              C.POINTER(AppearanceLoopParams), C.POINTER(LoopEdge), ip, fp, C.c_int, ip]
+    L.lsr_visibility_pairs.argtypes = [C.POINTER(SubMap), C.c_int, dp, C.POINTER(VisibilityParams), ip, ip, fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lsr_depth_images_build.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, C.POINTER(VisibilityParams), C.c_int, vp,
+                                         C.c_int]
+    L.lsr_visibility_votes.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, vp, C.c_int,
+                                       C.POINTER(VisibilityParams), vp, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.lsr_assemble_map_static.argtypes = [vp, C.POINTER(SubMap), C.c_int, C.POINTER(Pc2Layout), C.c_int, dp, vp, C.c_int,
+                                          C.POINTER(VisibilityParams), vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.lsr_parse_pcd_header.argtypes = [vp, C.c_size_t, C.POINTER(PcdInfo)]
     L.lsr_decode_pcd.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]
     L.lsr_load_pcd.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(Pc2Layout), C.c_int, C.POINTER(C.c_size_t)]

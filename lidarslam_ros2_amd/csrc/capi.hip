@@ -174,6 +174,8 @@ int lsr_get_f64(lsr_handle h, int key, double* v) {
     case LSR_POSE_SEARCH_MS: *v = h->pose_search.ms; return LSR_OK;
     case LSR_SCAN_CONTEXT_BUILD_MS: *v = h->scan_context.build_ms; return LSR_OK;
     case LSR_SCAN_CONTEXT_MATCH_MS: *v = h->scan_context.match_ms; return LSR_OK;
+    case LSR_DEPTH_IMAGES_MS: *v = h->visibility.images_ms; return LSR_OK;
+    case LSR_VISIBILITY_MS: *v = h->visibility.votes_ms; return LSR_OK;
     default: set_last_error("unknown f64 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -232,6 +234,9 @@ int lsr_set_i32(lsr_handle h, int key, int v) {
     case LSR_PCD_READ_COMPRESSED:
       if (v != 0 && v != 1) { set_last_error("LSR_PCD_READ_COMPRESSED must be 0 or 1"); return LSR_ERR_INVALID_ARGUMENT; }
       h->pcd_read.read_compressed = v; return LSR_OK;
+    case LSR_VISIBILITY_PIECE_BYTES:
+      if (v < VIS_PIECE_MIN || v > VIS_PIECE_MAX) { set_last_error("visibility piece size must be in 256 .. 1 << 30 bytes"); return LSR_ERR_INVALID_ARGUMENT; }
+      h->visibility.piece_bytes = v; return LSR_OK;
     default: set_last_error("unknown i32 key"); return LSR_ERR_INVALID_ARGUMENT;
   }
 }
@@ -260,6 +265,7 @@ int lsr_get_i32(lsr_handle h, int key, int* v) {
     case LSR_MAP_FILTER_KEY_BITS: *v = h->map_filter.key_bits; return LSR_OK;
     case LSR_PCD_PIECE_RECORDS: *v = h->pcd.piece_records; return LSR_OK;
     case LSR_PCD_READ_PIECE_BYTES: *v = h->pcd_read.piece_bytes; return LSR_OK;
+    case LSR_VISIBILITY_PIECE_BYTES: *v = h->visibility.piece_bytes; return LSR_OK;
     case LSR_PCD_READ_COMPRESSED: *v = h->pcd_read.read_compressed; return LSR_OK;
     case LSR_PCD_UNRESOLVED_TOKENS: *v = h->pcd_read.unresolved; return LSR_OK;
     case LSR_TARGET_PREPARED:

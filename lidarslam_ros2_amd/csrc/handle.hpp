@@ -4,6 +4,7 @@
 #include "deskew.hpp"
 #include "gicp.hpp"
 #include "map_filter.hpp"
+#include "map_visibility.hpp"
 #include "map_window.hpp"
 #include "ndt.hpp"
 #include "nn.hpp"
@@ -113,6 +114,8 @@ struct lsr_handle_s {
   lsr::PoseSearchState pose_search;   // lsr_ndt_score_poses / lsr_ndt_search_pose (csrc/pose_search.hip): pose and score buffers, kept between calls
 
   lsr::ScanContextState scan_context;   // lsr_scan_context_build / _match / lsr_search_loop_appearance (csrc/scan_context.hip): tables and staged descriptors, kept between calls
+
+  lsr::VisibilityState visibility;   // lsr_depth_images_build / lsr_visibility_votes / lsr_assemble_map_static (csrc/map_visibility.hip): tables, staged images, votes; kept between calls
 
   // worker objects of lsr_search_loop(top_k > 1) and lsr_ndt_search_pose: one per candidate registered in the same launch chain
   std::vector<std::unique_ptr<lsr_handle_s>> aux;

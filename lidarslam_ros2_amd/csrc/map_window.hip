@@ -116,6 +116,20 @@ __global__ __launch_bounds__(256) void mw_write_kernel(const unsigned char* __re
   }
 }
 
+}  // namespace
+
+int mw_scan_counts(BuildScratch& sc, hipStream_t stream, const int* counts, int nb, int* base, unsigned int* token) {
+  if (int st = sc.ensure_mailbox()) return st;
+  unsigned int t = ++sc.token;
+  if (t == 0) t = ++sc.token;
+  hipLaunchKernelGGL(mw_scan_kernel, dim3(1), dim3(MW_SCAN_WIDTH), 0, stream, counts, nb, base, sc.d_mb, t);
+  LSR_HIP(hipGetLastError());
+  *token = t;
+  return LSR_OK;
+}
+
+namespace {
+
 MfFields mw_fields(const lsr_pc2_layout* L) {
   return MfFields{(int)L->point_step, (int)L->offset_x, (int)L->offset_y, (int)L->offset_z, L->offset_intensity >= 0 ? (int)L->offset_intensity : -1};
 }
@@ -144,10 +158,9 @@ int mw_count(lsr_handle h, const void* d_in, size_t n, const MfFields& F, const 
   for (int k = 0; k < 3; k++) { C->W.lo[k] = (float)w->lo[k]; C->W.hi[k] = (float)w->hi[k]; }
   C->nb = (int)((n + MW_CHUNK - 1) / MW_CHUNK);
   int st;
-  if ((st = S.counts.reserve(2 * (size_t)C->nb + 1)) || (st = sc.ensure_mailbox())) return st;
+  if ((st = S.counts.reserve(2 * (size_t)C->nb + 1))) return st;
   if (h->profile && (st = S.ensure_events())) return st;
-  unsigned int token = ++sc.token;
-  if (token == 0) token = ++sc.token;
+  unsigned int token = 0;
   int* counts = S.counts.p;
   int* base = counts + C->nb;
   if (h->profile) LSR_HIP(hipEventRecord(S.ev[0], h->stream));
@@ -155,8 +168,8 @@ int mw_count(lsr_handle h, const void* d_in, size_t n, const MfFields& F, const 
     hipLaunchKernelGGL(mw_count_kernel<true>, dim3(C->nb), dim3(256), 0, h->stream, C->d_in, F, n, C->inv_leaf, C->W, counts);
   else
     hipLaunchKernelGGL(mw_count_kernel<false>, dim3(C->nb), dim3(256), 0, h->stream, C->d_in, F, n, C->inv_leaf, C->W, counts);
-  hipLaunchKernelGGL(mw_scan_kernel, dim3(1), dim3(MW_SCAN_WIDTH), 0, h->stream, counts, C->nb, base, sc.d_mb, token);
   LSR_HIP(hipGetLastError());
+  if ((st = mw_scan_counts(sc, h->stream, counts, C->nb, base, &token))) return st;
   if (h->profile) LSR_HIP(hipEventRecord(S.ev[1], h->stream));
   int total = 0;
   if ((st = sorted_runs_count(sc, h->stream, token, &total))) return st;

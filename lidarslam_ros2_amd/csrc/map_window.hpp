@@ -29,4 +29,9 @@ struct MapWindowState {
   }
 };
 
+// The scan of the cut, for whoever compacts records by a flag (map_visibility.hip does): base[b] = counts[0] + .. + counts[b - 1] for
+// b = 0 .. nb by ONE workgroup, enqueued on `stream`; the total also travels to sc's host mailbox under *token — sorted_runs_count
+// (sort.hpp) waits for it.  counts != base.
+int mw_scan_counts(BuildScratch& sc, hipStream_t stream, const int* counts, int nb, int* base, unsigned int* token);
+
 }  // namespace lsr

@@ -18,7 +18,7 @@ import numpy as np
 from . import _capi
 from .loop_closure import SubMap
 from .posemath import matrix_from_pose, quaternion_from_matrix
-from .registration import PC2_XYZI, ScanContextParams, _is_torch_cuda
+from .registration import PC2_XYZI, ScanContextParams, VisibilityParams, _is_torch_cuda
 
 
 def _as_float_records(records, point_step: int):
@@ -49,6 +49,10 @@ class MapArray:
         self._sc_table = None         # resident descriptor table of scan_contexts: (capacity, R, S) float32
         self._sc_count = 0            # submaps it holds
         self._sc_params = None
+        self._di_table = None         # resident eroded depth images of depth_images: (capacity, H, 4 W) float32
+        self._di_count = 0            # submaps it holds
+        self._di_params = None
+        self.last_static = None       # (records kept, records removed) of the last map assembled with remove_moving
 
     def __len__(self) -> int:
         return len(self.submaps)
@@ -62,27 +66,52 @@ class MapArray:
         self.submaps.append(sm)
         return sm
 
-    def publish_map(self, reg, out=None, leaf=None):
+    def publish_map(self, reg, out=None, leaf=None, remove_moving=None):
         """publishMap (:529-552): every submap moved by its stored pose, concatenated.  -> (records, first_record).  `leaf`: a leaf
-        size thins the map on the device before it leaves the call (Registration.voxelGridFilterMap) -> (records, None)."""
-        if leaf is None:
-            return reg.assembleMap(self.submaps, None, self.layout, self.layout, out)
-        return reg.assembleMap(self.submaps, None, self.layout, self.layout, out, leaf)
+        size thins the map on the device before it leaves the call (Registration.voxelGridFilterMap) -> (records, None).
+        `remove_moving`: VisibilityParams — the records a neighbouring keyframe saw through are left out first
+        (Registration.assembleMapStatic over depth_images; first_record then indexes the kept records)."""
+        return self._map(reg, None, out, leaf, remove_moving)
 
-    def modified_map(self, reg, poses, out=None, leaf=None):
+    def modified_map(self, reg, poses, out=None, leaf=None, remove_moving=None):
         """The map half of doPoseAdjustment (:321-368): every submap moved by the optimiser's estimate for it (4x4 fp64 each).
         records[first_record[i]:first_record[i + 1]] is modified_map_array.submaps[i].cloud (:343-351).  -> (records, first_record).
-        `leaf`: as for publish_map -> (records, None)."""
-        if leaf is None:
-            return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
-        return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out, leaf)
+        `leaf`, `remove_moving`: as for publish_map (the votes are taken under the same `poses`)."""
+        return self._map(reg, poses, out, leaf, remove_moving)
 
-    def save_map(self, reg, path, poses=None, data="ascii", leaf=None) -> int:
+    def _map(self, reg, poses, out, leaf, remove_moving):
+        if remove_moving is None:
+            if leaf is None:
+                return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out)
+            return reg.assembleMap(self.submaps, poses, self.layout, self.layout, out, leaf)
+        if leaf is None:
+            records, first, removed = reg.assembleMapStatic(self.submaps, self.depth_images(reg, remove_moving), remove_moving, poses,
+                                                            self.layout, self.layout, out)
+            self.last_static = (int(records.shape[0]), removed)
+            return records, first
+        static = self._static_on_device(reg, poses, remove_moving)
+        return reg.voxelGridFilterMap(static, float(leaf), self.layout, self.layout, out), None
+
+    def _static_on_device(self, reg, poses, remove_moving):
+        """The static map as records that stay on the device, whatever the residency of the submaps."""
+        records, _, removed = reg.assembleMapStatic(self.submaps, self.depth_images(reg, remove_moving), remove_moving, poses, self.layout,
+                                                    self.layout, None, device_out=True)
+        self.last_static = (int(records.shape[0]), removed)
+        return records
+
+    def save_map(self, reg, path, poses=None, data="ascii", leaf=None, remove_moving=None) -> int:
         """`pcl::io::savePCDFileASCII("map.pcd", *map_ptr)` at the end of doPoseAdjustment (:369): the map by the stored poses, or by
         the optimiser's `poses` when given (4x4 fp64 each), written to `path` as ASCII PCD with fields x y z intensity — one call into
         the registration object, the map never visits the host as records.  `data`: "ascii" (the default: those bytes), "binary" or
         "binary_compressed" (the LZF stream compressed on the device).  `leaf`: a leaf size thins the map on the device before it is
-        written (Registration.voxelGridFilterMap's records; their number: reg.getSavedMapPoints()).  -> the file's size in bytes."""
+        written (Registration.voxelGridFilterMap's records; their number: reg.getSavedMapPoints()).  `remove_moving`:
+        VisibilityParams — the static map (publish_map) is assembled on the device, thinned there when `leaf` is given, and written
+        from that buffer (Registration.savePCDFile); self.last_static = (kept, removed).  -> the file's size in bytes."""
+        if remove_moving is not None:
+            static = self._static_on_device(reg, poses, remove_moving)
+            if leaf is not None:
+                static = reg.voxelGridFilterMap(static, float(leaf), self.layout, self.layout)
+            return reg.savePCDFile(path, static, self.layout, data)
         if leaf is not None:   # the map thinned with this leaf size on the device before it is written
             return reg.saveMapPCDFile(path, self.submaps, poses, self.layout, data, leaf)
         if data == "ascii":
@@ -165,6 +194,38 @@ class MapArray:
         if self._sc_table is None:
             return np.zeros((0, R, S), np.float32)
         return self._sc_table[:n]
+
+    def depth_images(self, reg, params: VisibilityParams = VisibilityParams()):
+        """The eroded depth image of every submap, for Registration.assembleMapStatic: a resident table (on the device when the
+        submaps are) that grows geometrically and is extended by the submaps added since the last call only — an image depends on
+        its own cloud alone, not on any pose.  Other image parameters than last time start the table again.  -> (n, height,
+        4 face_width) float32, a view of that table, valid until the next call."""
+        params = VisibilityParams(*params)
+        key = (int(params.face_width), int(params.height), float(params.max_tan_elevation), float(params.min_range), float(params.max_range),
+               tuple(float(v) for v in params.sensor_origin))   # what an image depends on
+        H, W4 = params.shape
+        if self._di_params != key:
+            self._di_table, self._di_count, self._di_params = None, 0, key
+        n = len(self.submaps)
+        if n > self._di_count:
+            cap = 0 if self._di_table is None else int(self._di_table.shape[0])
+            if n > cap:
+                on_device = any(_is_torch_cuda(s.cloud) for s in self.submaps)
+                grown = self._empty(max(n, 2 * cap, 1) * H * W4 * 4, on_device, reg)
+                if on_device:
+                    import torch
+
+                    grown = grown.view(torch.float32).reshape(-1, H, W4)
+                else:
+                    grown = grown.view(np.float32).reshape(-1, H, W4)
+                if self._di_count:
+                    grown[: self._di_count] = self._di_table[: self._di_count]
+                self._di_table = grown
+            reg.depthImages(self.submaps[self._di_count:], params, self.layout, self._di_table[self._di_count:])
+            self._di_count = n
+        if self._di_table is None:
+            return np.zeros((0, H, W4), np.float32)
+        return self._di_table[:n]
 
     @staticmethod
     def _empty(nbytes: int, on_device: bool, reg):

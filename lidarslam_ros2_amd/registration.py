@@ -125,6 +125,71 @@ def scanContextGuess(candidate, latest, shift: int, num_sectors: int = 60) -> np
     return _col16_to_mat(g)
 
 
+class VisibilityParams(NamedTuple):
+    """lsr_visibility_params: the depth image of a keyframe is `height` rows x 4 `face_width` columns (four cube faces side by side)
+    out to +-max_tan_elevation and from min_range to max_range [m]; a record is voted against by a neighbouring keyframe (within
+    keyframe_range [m], the max_neighbours nearest) whose eroded image is more than `margin` [m] deeper where the record would be;
+    min_votes such votes take it out of the static map.  sensor_origin: the lidar in the keyframe's frame."""
+    face_width: int = 128
+    height: int = 32
+    max_tan_elevation: float = 0.5773502691896257   # tan 30 degrees
+    min_range: float = 0.5
+    max_range: float = 80.0
+    margin: float = 0.5
+    keyframe_range: float = 30.0
+    max_neighbours: int = 32
+    min_votes: int = 2
+    sensor_origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+
+    def struct(self) -> "capi.VisibilityParams":
+        return capi.VisibilityParams(int(self.face_width), int(self.height), float(self.max_tan_elevation), float(self.min_range),
+                                     float(self.max_range), float(self.margin), float(self.keyframe_range), int(self.max_neighbours),
+                                     int(self.min_votes), (C.c_double * 3)(*[float(v) for v in self.sensor_origin]))
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        """(rows, columns) of one image"""
+        return int(self.height), 4 * int(self.face_width)
+
+
+def _pose_table(submaps, poses):
+    """The lsr_submap array (poses only, no clouds) and the column-major fp64 poses (or None) of a host-only entry."""
+    n = len(submaps)
+    arr = (capi.SubMap * n)()
+    for i, sm in enumerate(submaps):
+        arr[i].position[:] = [float(v) for v in sm.position]
+        arr[i].orientation[:] = [float(v) for v in sm.orientation]
+        arr[i].distance = float(getattr(sm, "distance", 0.0))
+    P = None
+    if poses is not None:
+        if len(poses) != n:
+            raise ValueError("one pose per submap")
+        P = np.ascontiguousarray(np.stack([np.asarray(p, np.float64).reshape(4, 4).T.reshape(16) for p in poses]), np.float64)
+    return arr, P
+
+
+def visibilityPairs(submaps, poses=None, params: VisibilityParams = VisibilityParams()):
+    """Which keyframes look at which (lsr_visibility_pairs; needs no device): `submaps` = objects with `position` and `orientation`,
+    `poses` = None (the stored poses) or one 4x4 fp64 per submap.  -> (first_pair (n + 1,) int32, other (m,) int32, rel12 (m, 3, 4)
+    float32): the pairs of keyframe i are first_pair[i] .. first_pair[i + 1], other[p] = k, rel12[p] = the first three rows of
+    M_k^-1 M_i."""
+    n = len(submaps)
+    if n == 0:
+        raise ValueError("visibilityPairs needs at least one submap")
+    arr, P = _pose_table(submaps, poses)
+    cap = n * max(min(int(params.max_neighbours), n - 1), 1)
+    first = np.zeros(n + 1, np.int32)
+    other = np.zeros(cap, np.int32)
+    rel = np.zeros((cap, 12), np.float32)
+    m = C.c_size_t()
+    cp = VisibilityParams(*params).struct()
+    ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    capi.check(capi.load().lsr_visibility_pairs(arr, n, P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.byref(cp),
+                                                first.ctypes.data_as(ip), other.ctypes.data_as(ip), rel.ctypes.data_as(fp), cap,
+                                                C.byref(m)), "visibilityPairs")
+    return first, other[: m.value].copy(), rel[: m.value].reshape(-1, 3, 4).copy()
+
+
 def _window_struct(window) -> capi.MapWindow:
     leaf, lo, hi = window
     return capi.MapWindow(float(leaf), (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]))
@@ -762,6 +827,141 @@ class Registration:
         """hipEvent time [ms] of the launches of the last scanContext and of the last matchScanContext / search_loop_appearance
         comparison on this object (setProfiling(True)), else 0.  -> (build, match)"""
         return self._getf(capi.SCAN_CONTEXT_BUILD_MS), self._getf(capi.SCAN_CONTEXT_MATCH_MS)
+
+    # -- moving objects out of the map: visibility votes (SURVEY.md 8f N11) ---------------------------------
+    def _float_out(self, out, shape, on_device: bool, what: str):
+        """A float32 result buffer of `shape` -> (buffer, pointer, on_device); out: None = a new one."""
+        count = int(np.prod(shape))
+        if out is None:
+            if on_device:
+                import torch
+
+                out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", self._device))
+            else:
+                out = np.zeros(shape, np.float32)
+        if _is_torch_cuda(out):
+            import torch
+
+            if not out.is_contiguous() or out.dtype != torch.float32 or out.numel() < count:
+                raise ValueError(f"{what} must be a contiguous float32 buffer of {shape}")
+            _order_after_torch(self, out)
+            return out, out.data_ptr(), True
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable and out.size >= count):
+            raise ValueError(f"{what} must be a writeable contiguous float32 buffer of {shape}")
+        return out, out.ctypes.data, False
+
+    def depthImages(self, submaps, params: "VisibilityParams" = None, layout=PC2_XYZI, out=None, eroded: bool = True):
+        """The depth image of every submap through lsr_depth_images_build: one launch over all of them, and with `eroded` (the
+        default: what the votes compare against) the 3 x 3 minimum in one more.  `submaps` as for scanContext.  `out`: None = a new
+        buffer (a CUDA tensor when the clouds are), or the float32 buffer to write — a view of a resident table advanced by k images
+        appends.  -> (n, height, 4 face_width) float32; an empty pixel is +inf."""
+        params = VisibilityParams(*(params or VisibilityParams()))
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("depthImages needs at least one submap")
+        li = self._layout(*layout)
+        arr, keep, residency, _, _ = self._submap_table(submaps, None, int(layout[0]))
+        H, W4 = params.shape
+        out, optr, out_dev = self._float_out(out, (n, H, W4), bool(residency), "out")
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        cp = params.struct()
+        capi.check(self._lib.lsr_depth_images_build(self._h, arr, n, C.byref(li), 1 if residency else 0, C.byref(cp), 1 if eroded else 0,
+                                                    C.c_void_p(optr), 1 if out_dev else 0), "depthImages")
+        flat = out.view(-1) if out_dev else out.reshape(-1)
+        return flat[: n * H * W4].reshape(n, H, W4)
+
+    def _images_arg(self, images, n: int, params):
+        H, W4 = params.shape
+        if _is_torch_cuda(images):
+            import torch
+
+            t = images if images.is_contiguous() else images.contiguous()
+            if t.dtype != torch.float32 or t.numel() < n * H * W4:
+                raise ValueError("images must be float32 of shape (n, height, 4 face_width)")
+            _order_after_torch(self, t)
+            return t.data_ptr(), 1, t
+        t = np.ascontiguousarray(images, np.float32)
+        if t.size < n * H * W4:
+            raise ValueError("images must be float32 of shape (n, height, 4 face_width)")
+        return t.ctypes.data, 0, t
+
+    def visibilityVotes(self, submaps, images, params: "VisibilityParams" = None, poses=None, layout=PC2_XYZI, device_out: bool = False):
+        """The visibility votes against every record through lsr_visibility_votes: `images` = the ERODED depth images of the same
+        submaps (depthImages; numpy array or CUDA tensor), `poses` as for assembleMap.  -> (votes (total,) int32 in assembly order — a
+        CUDA tensor with device_out —, first_record (n + 1,) int64)."""
+        params = VisibilityParams(*(params or VisibilityParams()))
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("visibilityVotes needs at least one submap")
+        li = self._layout(*layout)
+        arr, keep, residency, total, P = self._submap_table(submaps, poses, int(layout[0]))
+        iptr, idev, ikeep = self._images_arg(images, n, params)   # ikeep: the buffer the call reads, kept alive until it returns
+        if device_out:
+            import torch
+
+            votes = torch.empty(max(total, 1), dtype=torch.int32, device=torch.device("cuda", self._device))
+            _order_after_torch(self, votes)
+            vptr = votes.data_ptr()
+        else:
+            votes = np.zeros(max(total, 1), np.int32)
+            vptr = votes.ctypes.data
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        first = (C.c_size_t * (n + 1))()
+        n_rec = C.c_size_t()
+        cp = params.struct()
+        capi.check(self._lib.lsr_visibility_votes(self._h, arr, n, C.byref(li), 1 if residency else 0,
+                                                  P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.c_void_p(iptr), idev,
+                                                  C.byref(cp), C.c_void_p(vptr), 1 if device_out else 0, first, C.byref(n_rec)),
+                   "visibilityVotes")
+        return votes[: n_rec.value], np.array(first[:], np.int64)
+
+    def assembleMapStatic(self, submaps, images, params: "VisibilityParams" = None, poses=None, in_layout=PC2_XYZI, out_layout=PC2_XYZI,
+                          out=None, device_out=None, count_only: bool = False):
+        """assembleMap without what moved (lsr_assemble_map_static): the records of assembleMap(submaps, poses, ...) with fewer than
+        params.min_votes visibility votes against them, in input order.  `images`: the eroded depth images of the same submaps
+        (depthImages / MapArray.depth_images).  `out` as for assembleMap; `device_out`: where a new buffer lives (None: where the
+        clouds are).  -> (records (kept, out point_step) uint8, first_record (n + 1,) int64 indexing the kept records, n_removed);
+        count_only: records is None and nothing is written."""
+        params = VisibilityParams(*(params or VisibilityParams()))
+        n = len(submaps)
+        if n == 0:
+            raise ValueError("assembleMapStatic needs at least one submap")
+        li, lo = self._layout(*in_layout), self._layout(*out_layout)
+        out_step = int(out_layout[0])
+        arr, keep, residency, total, P = self._submap_table(submaps, poses, int(in_layout[0]))
+        iptr, idev, ikeep = self._images_arg(images, n, params)   # ikeep: the buffer the call reads, kept alive until it returns
+        dev_holders = [h for h in keep if _is_torch_cuda(h)]
+        if dev_holders:
+            _order_after_torch(self, dev_holders[-1])
+        own = out is None
+        flat, optr, cap, out_dev = None, None, 0, False
+        if not count_only:
+            _, flat, optr, cap, out_dev = self._out_records(out, out_step, total, bool(residency) if device_out is None else bool(device_out))
+        first = (C.c_size_t * (n + 1))()
+        n_out, n_removed = C.c_size_t(), C.c_size_t()
+        cp = params.struct()
+        capi.check(self._lib.lsr_assemble_map_static(self._h, arr, n, C.byref(li), 1 if residency else 0,
+                                                     P.ctypes.data_as(C.POINTER(C.c_double)) if P is not None else None, C.c_void_p(iptr), idev,
+                                                     C.byref(cp), C.c_void_p(optr) if optr is not None else None, cap, C.byref(lo),
+                                                     1 if out_dev else 0, first, C.byref(n_out), C.byref(n_removed)), "assembleMapStatic")
+        records = None if count_only else self._trimmed(flat, int(n_out.value), out_step, cap, own)
+        return records, np.array(first[:], np.int64), int(n_removed.value)
+
+    def visibilityPieceBytes(self, nbytes: Optional[int] = None) -> int:
+        """Bytes per staging piece of host clouds in depthImages / visibilityVotes / assembleMapStatic (LSR_VISIBILITY_PIECE_BYTES,
+        256 .. 1 << 30): sets it when given, returns the current value.  The images and the votes do not depend on it."""
+        if nbytes is not None:
+            capi.check(self._lib.lsr_set_i32(self._h, capi.VISIBILITY_PIECE_BYTES, int(nbytes)), "visibilityPieceBytes")
+        return self._geti(capi.VISIBILITY_PIECE_BYTES)
+
+    def visibilityMs(self):
+        """hipEvent time [ms] of the launches of the last depthImages and of the last visibilityVotes / assembleMapStatic on this object
+        (setProfiling(True)), else 0.  -> (images, votes)"""
+        return self._getf(capi.DEPTH_IMAGES_MS), self._getf(capi.VISIBILITY_MS)
 
     def _submap_table(self, submaps, poses, in_step: int):
         """The lsr_submap array of assembleMap / saveMapPCDFileASCII -> (array, keepalives, on_device, total records, column-major
